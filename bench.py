@@ -6,7 +6,13 @@ BayesRSamplerV2 on a synthetic cohort resident in HBM (generated on the device, 
 "synthetic data spec").  Default workload: BASELINE configs[1] (C2), N = 100,000 individuals
 x P = 500,000 f32 genotypes, K = 4 (cva = 1e-4, 1e-3, 1e-2).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c1] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K sweeps, writes the chain's state if --dump-outputs is
+given and prints the result line.  --full adds what takes runs of its own: the roofline of the
+dominant kernel (two instrumented sweeps after the timed region) and the CPU baseline (the oracle on
+one pinned core, in a child process); without it the result line's 'roofline' and 'cpu_baseline'
+are null.
 
 For N > 1 the driver launches one process per GPU (torch.distributed.run); markers are
 column-sharded (contiguous blocks) and the residual is kept coherent by one ncclAllReduce per
@@ -127,13 +133,20 @@ def parse():
     ap.add_argument("--data-seed", type=int, default=20261015)
     ap.add_argument("--profile-solve", action="store_true", help="k_solve phase timers (diag)")
     ap.add_argument("--trace-sweeps", type=int, default=0, help="time N more sweeps one by one (diag)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the roofline "
+                         "of the dominant kernel (two instrumented sweeps) and the CPU baseline (a child process); "
+                         "without it 'roofline' and 'cpu_baseline' are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the chain's state as the last timed sweep left it (what a "
+                         "caller of the session reads back) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-markers", type=int, default=3000,
                     help="markers in the bounded CPU-baseline sample (N as in the config)")
     ap.add_argument("--cpu-sweeps", type=int, default=2, help="sweeps per timed repeat of the CPU sample")
     ap.add_argument("--cpu-repeats", type=int, default=3, help="timed repeats of the CPU sample (median reported)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-roofline-events", action="store_true")
+    ap.add_argument("--no-roofline-events", action="store_true", help="--full without the roofline sweeps")
     ap.add_argument("--exchanges", type=int, default=0,
                     help="column shards: residual exchanges per sweep E (0 = the library's automatic E = 8, whose "
                          "8-shard chain matches the 1-shard chain; 1 = north_star's one all-reduce per sweep, "
@@ -347,7 +360,7 @@ def main_oneshot(args):
     os.environ.pop("BRR_TIMELINE")
     rows = sum(1 for _ in open(out)) - 1
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-child", "--oneshot",
                "--cpu-iters", str(args.cpu_iters or MAXIT), "--data-seed", str(args.data_seed), "--seed", str(args.seed)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=3000)
@@ -369,6 +382,19 @@ def main_oneshot(args):
                                "thinning 10 (BASELINE configs[0], vignettes/BayesRR.Rmd:93-100)",
                    "wall_s": round(dt, 3), "csv_rows": rows, "csv_bytes": os.path.getsize(out), "timeline": tl},
         "roofline": None, "cpu_baseline": cpu}), flush=True)
+
+
+def dump_outputs(s, out_dir, rank, world):
+    """--dump-outputs: the chain's state after the last timed sweep, as a caller reads it back through
+    brr_session_get_scalar / get_vector (Session.state(); sigmaGG[0] is sigmaG), one float64 .npy per
+    name.  The largest, beta and comp, hold one double per marker of this rank's shard (4 MB each at
+    C2).  The data, the chain's seed and the Philox draws are fixed by the arguments, so two builds
+    that compute the same chain write the same files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in s.state().items():
+        fn = f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(out_dir, fn), np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 def main():
@@ -520,6 +546,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ms = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, rank, world)
     # fingerprint of the chain's state after the timed sweeps (A/B runs of library variants that must give
     # the same chain compare it)
     import hashlib
@@ -535,7 +563,7 @@ def main():
     # roofline of the dominant kernel (k_stream): HIP events around every streaming launch on
     # the session stream, over a few instrumented sweeps after the timed region
     roof = None
-    if not args.no_roofline_events:
+    if args.full and not args.no_roofline_events:
         # roofline of the dominant kernel, timed with HIP events on the session stream over two
         # instrumented sweeps after the timed region.  Fused mode: k_sweep is ONE launch per
         # sweep that streams this shard's whole X once (algorithmic bytes 4 N P); per-block mode:
@@ -620,7 +648,7 @@ def main():
             diag["block_events_us"] = block_events(s.vector(201), int(s.scalar(106)))
         s.set_scalar(102, 0.0)
     cpu = None
-    if rank == 0 and world == 1 and not emu and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not emu and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, P)
     if rank == 0:
         out = {

@@ -1,5 +1,5 @@
 """Turn two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over bench.py into the per-launch HBM
-traffic summary bench.py reads back (profiles/*_pmc.json).
+traffic summary bench.py --full reads back into its roofline (profiles/*_pmc.json).
 
 usage: pmc_json.py FETCH_DIR WRITE_DIR CONFIG BLOCK_SIZE X_STORAGE ALG_BYTES OUT
 
