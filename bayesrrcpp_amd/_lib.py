@@ -16,6 +16,15 @@ ORDER_BLOCKED, ORDER_REFERENCE, ORDER_IDENTITY = 0, 1, 2
 X_F32, X_2BIT = 0, 1  # brr_x_storage
 (MU, SIGMAE, SIGMAG, SIGMAF, TAU, ETA, C2, SUMSQ_BETA) = range(8)
 (BETA, COMP, EPS, SIGMAGG, PI, ALPHA, LAMBDA, XSQ, ORDER, VCOUNT, BETAACUM, HSV) = range(12)
+# brr_summary: posterior summaries over kept sweeps (brr_session_summary_get)
+(SUM_BETA_MEAN, SUM_BETA_SD, SUM_PIP, SUM_COMP_FREQ, SUM_G_MEAN, SUM_G_SD, SUM_WINDOW_PIP, SUM_WINDOW_SSQ,
+ SUM_WINDOW_SHARE, SUM_TRACE, SUM_BETA_M2, SUM_G_M2, SUM_COMP_COUNT, SUM_WINDOW_COUNT) = range(14)
+SUM_NAMES = ("beta_mean", "beta_sd", "pip", "comp_freq", "g_mean", "g_sd", "window_pip", "window_ssq",
+             "window_share", "trace", "beta_m2", "g_m2", "comp_count", "window_count")
+SUM_CLASS_ITEMS = (SUM_PIP, SUM_COMP_FREQ, SUM_COMP_COUNT)                                  # BayesR family only
+SUM_WINDOW_ITEMS = (SUM_WINDOW_PIP, SUM_WINDOW_SSQ, SUM_WINDOW_SHARE, SUM_WINDOW_COUNT)  # window > 0 only
+TRACE_HEADER = ("iteration", "mu", "sigmaE", "sigmaG", "sigmaF", "tau", "eta", "c2", "sumsq_beta", "var_g",
+                "h2", "nnz")
 ABI_VERSION = 4
 
 LOG_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
@@ -55,6 +64,9 @@ EXPORTED = [
     "brr_session_synchronize", "brr_session_linear_predictor",
     "brr_group_create", "brr_group_init", "brr_group_sweep", "brr_group_destroy",
     "brr_session_output_open", "brr_session_output_sample", "brr_session_output_close",
+    "brr_session_summary_begin", "brr_session_summary_accumulate", "brr_session_summary_run",
+    "brr_session_summary_count", "brr_session_summary_trace_width", "brr_session_summary_get",
+    "brr_session_summary_write", "brr_session_summary_end",
 ]
 
 _lib = None
@@ -145,6 +157,17 @@ def lib():
                                           C.c_int32, C.c_int32]
     L.brr_session_output_sample.argtypes = [vp, C.c_int32]
     L.brr_session_output_close.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.brr_session_summary_begin.argtypes = [vp, C.c_int32]
+    L.brr_session_summary_accumulate.argtypes = [vp]
+    L.brr_session_summary_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.brr_session_summary_count.restype = C.c_int32
+    L.brr_session_summary_count.argtypes = [vp]
+    L.brr_session_summary_trace_width.restype = C.c_int32
+    L.brr_session_summary_trace_width.argtypes = [vp]
+    L.brr_session_summary_get.restype = C.c_int64
+    L.brr_session_summary_get.argtypes = [vp, C.c_int32, D]
+    L.brr_session_summary_write.argtypes = [vp, C.c_char_p]
+    L.brr_session_summary_end.argtypes = [vp]
     _lib = L
     return L
 

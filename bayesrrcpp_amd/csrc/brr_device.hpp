@@ -169,4 +169,26 @@ struct Dev {
   Scal *sc;
 };
 
+// Posterior summaries accumulated over kept sweeps (brr_summary.hpp, brr_session_summary_*): the
+// accumulators of one session, by value to the k_summary_* kernels.
+//   row      f64 [width + 1] the sweep's trace row (include/brr.h: 12 header values, count[g][k],
+//            ssq[g][k]; width = 12 + 2 GK, GK = G K, Horseshoe 1), then the sweep's total sum beta^2
+//            (k_summary_windows' denominator)
+//   mslab    f64 [MRG][2 GK + 2] per-workgroup counts, sums of beta^2, total, nnz (k_summary_markers)
+//   rslab    f64 [cdiv(N, 256)][3] per-workgroup (rows, mean, centred M2) of g (k_summary_rows)
+//   cnt      int [2] last-arriver tickets of the two kernels (zero between launches)
+struct SumDev {
+  double *bmean, *bM2;      // [M] Welford mean / centred sum of squares of beta
+  double *gmean, *gM2;      // [N] the same of the genetic value g
+  const double *Y;          // [N] the phenotype (restart sessions: the reconstructed mu + X beta + eps)
+  uint32_t *cfreq;          // [M][K] sweeps with comp[m] == k (BayesR family, else nullptr)
+  uint32_t *wany;           // [nW] sweeps in which a marker of the window is in the model
+  double *wshare, *wssq;    // [nW] running means of the window's share of sum beta^2, and of its sum beta^2
+  double *mslab, *rslab, *row;
+  int *cnt;
+  int width;                // 12 + 2 GK
+  int W;                    // markers per window (0: none)
+  int64_t nW;               // ceil(M / W)
+};
+
 }  // namespace brr

@@ -5067,6 +5067,10 @@ __global__ __launch_bounds__(256) void k_linpred(Dev d, double *out) {
   out[i] = acc;
 }
 
+// ------------------------------------------------------------------------------------
+// Posterior summaries over kept sweeps (k_summary_*)
+#include "brr_summary.hpp"
+
 }  // namespace brr
 
 // ======================================================================================
@@ -5575,6 +5579,29 @@ hipError_t launch_slab_sentinels(const Dev &d, int nrow, hipStream_t st) {
 
 hipError_t launch_markers(const Dev &d, int mode, uint32_t it, hipStream_t st) {
   hipLaunchKernelGGL(k_markers, dim3((unsigned)d.MRG), dim3(256), 0, st, d, mode, it);
+  return hipGetLastError();
+}
+
+// one kept sweep into the running summaries (brr_summary.hpp): markers, then the windows (they read
+// the sweep's total sum beta^2 from the trace row), then the rows (var_g / h2 complete the row)
+hipError_t launch_summary(const Dev &d, const SumDev &q, int n, int iteration, hipStream_t st) {
+  const double nd = (double)n;
+  hipLaunchKernelGGL(k_summary_markers, dim3((unsigned)d.MRG), dim3(256), 0, st, d, q, nd, (double)iteration);
+  if (q.W > 0) {
+    if (q.W <= SUM_W_THREAD)
+      hipLaunchKernelGGL(k_summary_windows<0>, dim3(cdiv64(q.nW, 256)), dim3(256), 0, st, d, q, nd);
+    else if (q.W <= SUM_W_WAVE)
+      hipLaunchKernelGGL(k_summary_windows<1>, dim3(cdiv64(q.nW, 4)), dim3(256), 0, st, d, q, nd);
+    else
+      hipLaunchKernelGGL(k_summary_windows<2>, dim3((unsigned)q.nW), dim3(256), 0, st, d, q, nd);
+  }
+  hipLaunchKernelGGL(k_summary_rows, dim3(cdiv64(d.N, 256)), dim3(256), 0, st, d, q, nd);
+  return hipGetLastError();
+}
+
+hipError_t launch_summary_yrec(const Dev &d, double *y, hipStream_t st) {
+  hipLaunchKernelGGL(k_linpred, dim3(cdiv64(d.N, 256)), dim3(256), 0, st, d, y);
+  hipLaunchKernelGGL(k_summary_yrec, dim3(cdiv64(d.N, 256)), dim3(256), 0, st, d, y);
   return hipGetLastError();
 }
 

@@ -63,6 +63,9 @@ size_t solve_lds_bytes(int B, int K);
 hipError_t launch_linpred(const Dev &d, double *out, hipStream_t st);
 hipError_t launch_slab_sentinels(const Dev &d, int nrow, hipStream_t st);  // fused solver's dot slots (epoch p in slot p)
 hipError_t launch_markers(const Dev &d, int mode, uint32_t it, hipStream_t st);
+// posterior summaries (brr_summary.hpp): kept sweep number n (1-based) folded into q's accumulators
+hipError_t launch_summary(const Dev &d, const SumDev &q, int n, int iteration, hipStream_t st);
+hipError_t launch_summary_yrec(const Dev &d, double *y, hipStream_t st);  // y = mu + X beta + F alpha + eps
 hipError_t launch_hyper(const Dev &d, uint32_t it, const double *stats, hipStream_t st);
 hipError_t launch_hyper_init(const Dev &d, const double *stats, bool pi_given, hipStream_t st);
 

@@ -264,6 +264,14 @@ int run_chain(brr_session *s, const Run &r, CsvWriter *w, int64_t *n_ok) {
   int64_t n_rows = 0;
   const char *rd = getenv("BRR_SAMPLE_RING");
   if (int rc = brr::sample_ring_open(s, rd ? atoi(rd) : 4)) return rc;
+  // BRR_SUMMARY_PREFIX: the posterior summaries of the kept iterations beside the CSV (windows of
+  // BRR_SUMMARY_WINDOW markers, default none), written as <prefix>.*.csv before returning
+  const char *sum_prefix = getenv("BRR_SUMMARY_PREFIX");
+  if (sum_prefix && !sum_prefix[0]) sum_prefix = nullptr;
+  if (sum_prefix) {
+    const char *sw = getenv("BRR_SUMMARY_WINDOW");
+    if (int rc = brr_session_summary_begin(s, sw ? atoi(sw) : 0)) return rc;
+  }
   w->bind(s, r.model, r.N, r.M, r.G, r.F);
   const auto t1 = std::chrono::steady_clock::now();
   const int every = r.max_it / 10;  // (int)std::ceil(max_iterations/10): integer division
@@ -293,6 +301,8 @@ int run_chain(brr_session *s, const Run &r, CsvWriter *w, int64_t *n_ok) {
       int slot = -1;
       if (int rc = brr::sample_ring_push(s, &slot)) return rc;
       w->sample(slot, it);
+      if (sum_prefix)
+        if (int rc = brr::summary_fold(s, it)) return rc;
       ++n_rows;
       t_push += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
       ++n_push;
@@ -308,6 +318,8 @@ int run_chain(brr_session *s, const Run &r, CsvWriter *w, int64_t *n_ok) {
     }
   }
   brr_session_synchronize(s);
+  if (sum_prefix)
+    if (int rc = brr_session_summary_write(s, sum_prefix)) return rc;
   const auto t2 = std::chrono::steady_clock::now();
   r.log("duration: " + std::to_string((long long)std::chrono::duration_cast<std::chrono::seconds>(t2 - t1).count()) + "s\n");
   return 0;

@@ -39,6 +39,10 @@ int sample_ring_max_in_use(brr_session *s);  // diagnostics: most slots ever tak
 // iterations instead of after each sweep, so the host keeps the device queue full
 int session_sweep(brr_session *s, int n, bool check);
 
+// posterior summaries (brr_session_summary_*): the current state folded in as kept sweep `iteration`
+// of the caller's loop (brr_session_summary_accumulate records the session's own sweep counter)
+int summary_fold(brr_session *s, int iteration);
+
 // a caller's options over the defaults, by the caller's ABI version: an older caller's struct
 // ends before the fields a later ABI added (ABI 1: row shards, ABI 2: exchanges_per_sweep)
 brr_options options_from_caller(const brr_options *in);

@@ -134,6 +134,31 @@ struct SampleRing {
   std::condition_variable cv;
 };
 
+// posterior summaries over kept sweeps (brr_session_summary_*, brr_summary.hpp).  The device
+// buffers are the summary's own (not in brr_session::allocs): summary_end frees them.
+struct Summary {
+  static constexpr int RING = 64;  // pinned trace rows in flight before a fold has to synchronise
+  SumDev q{};
+  int window = 0, width = 0, n = 0;  // n: kept sweeps folded in
+  double *yrec = nullptr;            // restart sessions: the reconstructed phenotype (q.Y)
+  double *pin = nullptr;             // [RING][width + 1] pinned copies of the device trace row
+  int pending = 0;                   // rows copied into pin (asynchronously) and not yet appended
+  std::vector<double> trace;         // [n - pending][width]
+  std::vector<void *> allocs;
+  void release() {
+    for (void *p : allocs) (void)hipFree(p);
+    allocs.clear();
+    if (pin) (void)hipHostFree(pin);
+    pin = nullptr;
+  }
+  // the stream has been synchronised: every pending row has landed
+  void drain() {
+    for (int i = 0; i < pending; ++i)
+      trace.insert(trace.end(), pin + (size_t)i * (width + 1), pin + (size_t)i * (width + 1) + width);
+    pending = 0;
+  }
+};
+
 struct brr_session {
   brr_options opt;
   Logger log;
@@ -195,6 +220,8 @@ struct brr_session {
   int64_t n_stream = 0, n_solve = 0, n_solve_sweep = 0;
   std::vector<void *> allocs;
   SampleRing ring;
+  Summary *sum = nullptr;  // between summary_begin and summary_end
+  bool in_group = false;   // member of a brr_group
 
   bool alloc_failed = false;  // after one failed allocation the rest are not attempted
   template <class T>
@@ -219,6 +246,7 @@ struct brr_session {
     if (st_side) (void)hipStreamSynchronize(st_side);
     if (st) (void)hipStreamSynchronize(st);
     brr::sample_ring_close(this);
+    if (sum) { sum->release(); delete sum; }
     if (comm) (void)ncclCommDestroy(comm);
     for (void *p : allocs) (void)hipFree(p);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
@@ -368,6 +396,7 @@ int upload_order(brr_session *s, const std::vector<int32_t> &order) {
 // still run in the same sweep
 int check_device_error(brr_session *s, bool mid_sweep = false) {
   HIPCHK(hipStreamSynchronize(s->st));
+  if (s->sum) s->sum->drain();  // the summary's trace rows copied so far have landed
   std::vector<int> sy(SY_WORDS);
   HIPCHK(hipMemcpy(sy.data(), s->d.sync, sizeof(int) * SY_WORDS, hipMemcpyDeviceToHost));
   if (sy[SY_ERR]) {
@@ -2157,6 +2186,7 @@ brr_group *brr_group_create(brr_session *const *members, int32_t n) {
     }
     g->c.ss.push_back(s);
   }
+  for (brr_session *s : g->c.ss) s->in_group = true;
   return g;
 }
 
@@ -2182,6 +2212,333 @@ int brr_session_synchronize(brr_session *s) {
   if (!s) return -1;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->st));
+  if (s->sum) s->sum->drain();
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// Posterior summaries over kept sweeps (include/brr.h; kernels in brr_summary.hpp)
+namespace {
+
+// the session has a summary: every brr_session_summary_* call but begin starts here
+Summary *summary_of(brr_session *s, const char *what) {
+  if (!s) { set_error("%s: null session", what); return nullptr; }
+  if (!s->sum) { set_error("%s: no summary (brr_session_summary_begin first)", what); return nullptr; }
+  return s->sum;
+}
+
+int summary_sync(brr_session *s) {
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->st));
+  s->sum->drain();
+  return 0;
+}
+
+void summary_drop(brr_session *s) {
+  if (!s->sum) return;
+  (void)hipSetDevice(s->device);
+  (void)hipStreamSynchronize(s->st);  // no fold may still write the buffers
+  s->sum->release();
+  delete s->sum;
+  s->sum = nullptr;
+}
+
+const char *kSummaryNames[] = {"BETA_MEAN", "BETA_SD", "PIP", "COMP_FREQ", "G_MEAN", "G_SD", "WINDOW_PIP",
+                               "WINDOW_SSQ", "WINDOW_SHARE", "TRACE", "BETA_M2", "G_M2", "COMP_COUNT",
+                               "WINDOW_COUNT"};
+
+}  // namespace
+
+int brr::summary_fold(brr_session *s, int iteration) {
+  Summary *u = summary_of(s, "summary_accumulate");
+  if (!u) return -1;
+  HIPCHK(hipSetDevice(s->device));
+  if (int rc = ensure_reduced(s)) return rc;
+  if (u->pending == Summary::RING)  // every pinned row is in flight: the one place a fold waits
+    if (int rc = summary_sync(s)) return rc;
+  HIPCHK(launch_summary(s->d, u->q, u->n + 1, iteration, s->st));
+  HIPCHK(hipMemcpyAsync(u->pin + (size_t)u->pending * (u->width + 1), u->q.row, sizeof(double) * (u->width + 1),
+                        hipMemcpyDeviceToHost, s->st));
+  u->n++;
+  u->pending++;
+  return 0;
+}
+
+extern "C" {
+
+int brr_session_summary_begin(brr_session *s, int32_t window) {
+  if (!s) { set_error("summary_begin: null session"); return -1; }
+  if (!s->initialized) { set_error("summary_begin: session not initialised (brr_session_init)"); return -1; }
+  if (s->nshard > 1 || s->nrshard > 1 || s->in_group) {
+    set_error("summary_begin: summaries of column- or row-sharded sessions are not supported "
+              "(shard_count %d, row_shard_count %d%s)", s->nshard, s->nrshard, s->in_group ? ", brr_group member" : "");
+    return -1;
+  }
+  if (window < 0) { set_error("summary_begin: window %d < 0", (int)window); return -1; }
+  HIPCHK(hipSetDevice(s->device));
+  summary_drop(s);  // a second begin resets the summary
+  const bool hs = s->model == MODEL_HORSESHOE;
+  const bool restart = s->model == MODEL_RESTART;
+  const int GK = hs ? 1 : s->G * s->K;
+  const int64_t M = s->M, N = s->N, nW = window > 0 ? (M + window - 1) / window : 0;
+  const int64_t nrg = (N + 255) / 256;
+  Summary *u = new Summary();
+  u->window = window;
+  u->width = 12 + 2 * GK;
+  SumDev &q = u->q;
+  q.width = u->width;
+  q.W = window;
+  q.nW = nW;
+  // (bytes, for the message of a failed allocation)
+  const long long bytes = 16 * M + 16 * N + (hs ? 0 : 4 * M * s->K) + (restart ? 8 * N : 0) + 20 * nW +
+                          8 * ((long long)s->d.MRG * (2 * GK + 2) + 3 * nrg + u->width + 1) + 8;
+  int rc = 0;
+  auto take = [&](auto **p, int64_t n) {
+    if (rc) { *p = nullptr; return; }
+    rc = dalloc(p, n);
+    if (!rc) {
+      u->allocs.push_back((void *)*p);
+      if (hipMemsetAsync((void *)*p, 0, sizeof(**p) * (size_t)std::max<int64_t>(n, 1), s->st) != hipSuccess) rc = -2;
+    }
+  };
+  take(&q.bmean, M);
+  take(&q.bM2, M);
+  take(&q.gmean, N);
+  take(&q.gM2, N);
+  if (!hs) take(&q.cfreq, M * s->K);
+  if (restart) take(&u->yrec, N);
+  if (window > 0) {
+    take(&q.wany, nW);
+    take(&q.wshare, nW);
+    take(&q.wssq, nW);
+  }
+  take(&q.mslab, (int64_t)s->d.MRG * (2 * GK + 2));
+  take(&q.rslab, 3 * nrg);
+  take(&q.row, u->width + 1);
+  take(&q.cnt, 2);
+  if (!rc && hipHostMalloc((void **)&u->pin, sizeof(double) * Summary::RING * (u->width + 1), hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    u->pin = nullptr;
+    rc = -2;
+  }
+  if (rc) {
+    const std::string why = brr_last_error();
+    (void)hipStreamSynchronize(s->st);
+    u->release();
+    delete u;
+    set_error("summary_begin: the accumulators do not fit (%lld bytes: M %lld, N %lld, K %d, windows %lld): %s",
+              bytes, (long long)M, (long long)N, s->K, (long long)nW, why.c_str());
+    return -2;
+  }
+  q.Y = s->d.Y;
+  s->sum = u;
+  if (restart) {
+    // no Y in a restart session: mu + X beta + eps of the state as it is now (one pass over X)
+    if (int rc2 = ensure_reduced(s)) { summary_drop(s); return rc2; }
+    if (launch_summary_yrec(s->d, u->yrec, s->st) != hipSuccess) {
+      set_error("summary_begin: %s", hipGetErrorString(hipGetLastError()));
+      summary_drop(s);
+      return -2;
+    }
+    q.Y = u->yrec;
+  }
+  if (hipStreamSynchronize(s->st) != hipSuccess) {
+    set_error("summary_begin: %s", hipGetErrorString(hipGetLastError()));
+    summary_drop(s);
+    return -2;
+  }
+  return 0;
+}
+
+int brr_session_summary_accumulate(brr_session *s) {
+  if (!summary_of(s, "summary_accumulate")) return -1;
+  return brr::summary_fold(s, s->iteration - 1);
+}
+
+int brr_session_summary_run(brr_session *s, int32_t max_iterations, int32_t burn_in, int32_t thinning) {
+  if (!summary_of(s, "summary_run")) return -1;
+  if (max_iterations < burn_in || max_iterations < 1 || burn_in < 1 || thinning < 1) {  // the one-shots' rule
+    set_error("summary_run: burn_in has to be a positive integer and smaller than the maximum number of "
+              "iterations, thinning positive (max_iterations %d, burn_in %d, thinning %d)",
+              (int)max_iterations, (int)burn_in, (int)thinning);
+    return 1;
+  }
+  for (int it = 0; it < max_iterations; ++it) {
+    // the device check every 16 iterations and at the end, as the one-shots' loop
+    const bool check = (it & 15) == 15 || it + 1 == max_iterations;
+    if (int rc = brr::session_sweep(s, 1, check)) return rc;
+    if (it >= burn_in && it % thinning == 0)
+      if (int rc = brr::summary_fold(s, it)) return rc;
+  }
+  return summary_sync(s);
+}
+
+int32_t brr_session_summary_count(brr_session *s) {
+  Summary *u = summary_of(s, "summary_count");
+  if (!u) return -1;
+  if (u->pending && summary_sync(s)) return -2;
+  return u->n;
+}
+
+int32_t brr_session_summary_trace_width(brr_session *s) {
+  Summary *u = summary_of(s, "summary_trace_width");
+  return u ? u->width : -1;
+}
+
+int64_t brr_session_summary_get(brr_session *s, int32_t which, double *out) {
+  Summary *u = summary_of(s, "summary_get");
+  if (!u) return -1;
+  const bool hs = s->model == MODEL_HORSESHOE;
+  int64_t n = -1;
+  switch (which) {
+    case BRR_SUM_PIP:
+      if (hs) break;
+      n = s->M; break;
+    case BRR_SUM_BETA_MEAN: case BRR_SUM_BETA_SD: case BRR_SUM_BETA_M2: n = s->M; break;
+    case BRR_SUM_COMP_FREQ: case BRR_SUM_COMP_COUNT:
+      if (hs) break;
+      n = s->M * s->K; break;
+    case BRR_SUM_G_MEAN: case BRR_SUM_G_SD: case BRR_SUM_G_M2: n = s->N; break;
+    case BRR_SUM_WINDOW_PIP: case BRR_SUM_WINDOW_SSQ: case BRR_SUM_WINDOW_SHARE: case BRR_SUM_WINDOW_COUNT:
+      if (u->window == 0) { set_error("summary_get: %s needs windows (summary_begin with window > 0)", kSummaryNames[which]); return -1; }
+      n = u->q.nW; break;
+    case BRR_SUM_TRACE: n = (int64_t)u->n * u->width; break;
+    default: set_error("summary_get: unknown item %d", (int)which); return -1;
+  }
+  if (n < 0) { set_error("summary_get: %s is class-based: the Horseshoe has no mixture classes", kSummaryNames[which]); return -1; }
+  if (!out) return n;
+  if (int rc = summary_sync(s)) return rc;
+  const double kept = (double)u->n;
+  auto counts = [&](const uint32_t *src, int64_t len, std::vector<uint32_t> *c) {
+    c->resize((size_t)len);
+    return d2h(s, c->data(), src, len);
+  };
+  std::vector<uint32_t> c;
+  int rc = 0;
+  switch (which) {
+    case BRR_SUM_BETA_MEAN: rc = d2h(s, out, u->q.bmean, n); break;
+    case BRR_SUM_G_MEAN: rc = d2h(s, out, u->q.gmean, n); break;
+    case BRR_SUM_WINDOW_SSQ: rc = d2h(s, out, u->q.wssq, n); break;
+    case BRR_SUM_WINDOW_SHARE: rc = d2h(s, out, u->q.wshare, n); break;
+    case BRR_SUM_BETA_M2: case BRR_SUM_BETA_SD: case BRR_SUM_G_M2: case BRR_SUM_G_SD: {
+      const bool beta = which == BRR_SUM_BETA_M2 || which == BRR_SUM_BETA_SD;
+      rc = d2h(s, out, beta ? u->q.bM2 : u->q.gM2, n);
+      if (!rc && (which == BRR_SUM_BETA_SD || which == BRR_SUM_G_SD))
+        for (int64_t i = 0; i < n; ++i) out[i] = u->n < 2 ? 0.0 : std::sqrt(out[i] / (kept - 1.0));
+      break;
+    }
+    case BRR_SUM_PIP:
+      rc = counts(u->q.cfreq, s->M * s->K, &c);
+      for (int64_t m = 0; !rc && m < n; ++m) out[m] = u->n ? 1.0 - (double)c[(size_t)(m * s->K)] / kept : 0.0;
+      break;
+    case BRR_SUM_COMP_FREQ: case BRR_SUM_COMP_COUNT:
+      rc = counts(u->q.cfreq, n, &c);
+      for (int64_t i = 0; !rc && i < n; ++i)
+        out[i] = which == BRR_SUM_COMP_COUNT ? (double)c[(size_t)i] : (u->n ? (double)c[(size_t)i] / kept : 0.0);
+      break;
+    case BRR_SUM_WINDOW_PIP: case BRR_SUM_WINDOW_COUNT:
+      rc = counts(u->q.wany, n, &c);
+      for (int64_t i = 0; !rc && i < n; ++i)
+        out[i] = which == BRR_SUM_WINDOW_COUNT ? (double)c[(size_t)i] : (u->n ? (double)c[(size_t)i] / kept : 0.0);
+      break;
+    case BRR_SUM_TRACE: std::copy(u->trace.begin(), u->trace.end(), out); break;
+  }
+  return rc ? rc : n;
+}
+
+int brr_session_summary_write(brr_session *s, const char *prefix) {
+  Summary *u = summary_of(s, "summary_write");
+  if (!u) return -1;
+  if (!prefix) { set_error("summary_write: null prefix"); return -1; }
+  const bool hs = s->model == MODEL_HORSESHOE;
+  auto get = [&](int which, std::vector<double> *v) -> int {
+    const int64_t n = brr_session_summary_get(s, which, nullptr);
+    if (n < 0) return (int)n;
+    v->assign((size_t)n, 0.0);
+    const int64_t r = n ? brr_session_summary_get(s, which, v->data()) : 0;
+    return r < 0 ? (int)r : 0;
+  };
+  auto open = [&](const char *ext) -> FILE * {
+    const std::string path = std::string(prefix) + ext;
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) set_error("summary_write: cannot open %s", path.c_str());
+    return f;
+  };
+  auto close = [&](FILE *f, const char *ext) -> int {
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) { set_error("summary_write: writing %s%s failed", prefix, ext); return -3; }
+    return 0;
+  };
+  std::vector<double> a, b, c, e;
+  {  // markers
+    if (int rc = get(BRR_SUM_BETA_MEAN, &a)) return rc;
+    if (int rc = get(BRR_SUM_BETA_SD, &b)) return rc;
+    if (!hs) {
+      if (int rc = get(BRR_SUM_PIP, &c)) return rc;
+      if (int rc = get(BRR_SUM_COMP_FREQ, &e)) return rc;
+    }
+    FILE *f = open(".markers.csv");
+    if (!f) return -3;
+    fputs("marker,mean,sd", f);
+    if (!hs) {
+      fputs(",pip", f);
+      for (int k = 0; k < s->K; ++k) fprintf(f, ",freq_%d", k);
+    }
+    fputc('\n', f);
+    for (int64_t m = 0; m < s->M; ++m) {
+      fprintf(f, "%lld,%.17g,%.17g", (long long)(s->col_offset + m), a[(size_t)m], b[(size_t)m]);
+      if (!hs) {
+        fprintf(f, ",%.17g", c[(size_t)m]);
+        for (int k = 0; k < s->K; ++k) fprintf(f, ",%.17g", e[(size_t)(m * s->K + k)]);
+      }
+      fputc('\n', f);
+    }
+    if (int rc = close(f, ".markers.csv")) return rc;
+  }
+  {  // rows
+    if (int rc = get(BRR_SUM_G_MEAN, &a)) return rc;
+    if (int rc = get(BRR_SUM_G_SD, &b)) return rc;
+    FILE *f = open(".rows.csv");
+    if (!f) return -3;
+    fputs("row,g_mean,g_sd\n", f);
+    for (int64_t i = 0; i < s->N; ++i) fprintf(f, "%lld,%.17g,%.17g\n", (long long)i, a[(size_t)i], b[(size_t)i]);
+    if (int rc = close(f, ".rows.csv")) return rc;
+  }
+  if (u->window > 0) {
+    if (int rc = get(BRR_SUM_WINDOW_PIP, &a)) return rc;
+    if (int rc = get(BRR_SUM_WINDOW_SSQ, &b)) return rc;
+    if (int rc = get(BRR_SUM_WINDOW_SHARE, &c)) return rc;
+    FILE *f = open(".windows.csv");
+    if (!f) return -3;
+    fputs("first_marker,pip,ssq,share\n", f);
+    for (int64_t w = 0; w < u->q.nW; ++w)
+      fprintf(f, "%lld,%.17g,%.17g,%.17g\n", (long long)(s->col_offset + w * u->window), a[(size_t)w], b[(size_t)w],
+              c[(size_t)w]);
+    if (int rc = close(f, ".windows.csv")) return rc;
+  }
+  {  // trace
+    if (int rc = get(BRR_SUM_TRACE, &a)) return rc;
+    FILE *f = open(".trace.csv");
+    if (!f) return -3;
+    fputs("iteration,mu,sigmaE,sigmaG,sigmaF,tau,eta,c2,sumsq_beta,var_g,h2,nnz", f);
+    const int G = hs ? 1 : s->G, K = hs ? 1 : s->K;
+    for (const char *name : {"count", "ssq"})
+      for (int g = 0; g < G; ++g)
+        for (int k = 0; k < K; ++k) fprintf(f, ",%s_%d_%d", name, g, k);
+    fputc('\n', f);
+    for (int r = 0; r < u->n; ++r)
+      for (int j = 0; j < u->width; ++j)
+        fprintf(f, "%.17g%c", a[(size_t)r * u->width + j], j + 1 == u->width ? '\n' : ',');
+    if (int rc = close(f, ".trace.csv")) return rc;
+  }
+  return 0;
+}
+
+int brr_session_summary_end(brr_session *s) {
+  if (!summary_of(s, "summary_end")) return -1;
+  summary_drop(s);
   return 0;
 }
 

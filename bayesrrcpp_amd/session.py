@@ -243,6 +243,61 @@ class Session:
         L.check(L.lib().brr_session_output_close(self.h, C.byref(m)), "output_close")
         return m.value
 
+    # -- posterior summaries over kept sweeps (brr_session_summary_*) ---------------------------
+    def summary_begin(self, window=0):
+        """Allocate (or reset) the device accumulators: effect means / SDs, PIPs, class frequencies,
+        genetic values, the per-sweep trace and, with window > 0, window inclusion probabilities."""
+        L.check(L.lib().brr_session_summary_begin(self.h, window), "summary_begin")
+        self._sum_window = window
+        return self
+
+    def summary_accumulate(self):
+        """Fold the current state in (no host synchronisation)."""
+        L.check(L.lib().brr_session_summary_accumulate(self.h), "summary_accumulate")
+        return self
+
+    def summary_run(self, max_iterations, burn_in, thinning):
+        """The one-shots' loop without the CSV: a sweep per iteration, the state folded in when
+        it >= burn_in and it % thinning == 0."""
+        L.check(L.lib().brr_session_summary_run(self.h, max_iterations, burn_in, thinning), "summary_run")
+        return self
+
+    @property
+    def summary_count(self):
+        n = L.lib().brr_session_summary_count(self.h)
+        if n < 0:
+            raise L.BrrError(f"summary_count: {L.last_error()}")
+        return n
+
+    def summary(self, which):
+        """One item (L.SUM_*) as a numpy array; COMP_FREQ / COMP_COUNT are M x K, TRACE kept x width."""
+        n = L.lib().brr_session_summary_get(self.h, which, None)
+        if n < 0:
+            raise L.BrrError(f"summary({which}): {L.last_error()}")
+        out = np.zeros(n, dtype=np.float64)
+        if n and L.lib().brr_session_summary_get(self.h, which, _d(out)) < 0:
+            raise L.BrrError(f"summary({which}): {L.last_error()}")
+        if which in (L.SUM_COMP_FREQ, L.SUM_COMP_COUNT):
+            return out.reshape(self.M, self.K)
+        if which == L.SUM_TRACE:
+            return out.reshape(-1, L.lib().brr_session_summary_trace_width(self.h))
+        return out
+
+    def posterior(self):
+        """Every item the model has, by name (L.SUM_NAMES): no class items for the Horseshoe, no
+        window items without windows."""
+        skip = set(L.SUM_CLASS_ITEMS if self.model == L.MODEL_HORSESHOE else ())
+        if not getattr(self, "_sum_window", 0):
+            skip.update(L.SUM_WINDOW_ITEMS)
+        return {name: self.summary(w) for w, name in enumerate(L.SUM_NAMES) if w not in skip}
+
+    def summary_write(self, prefix):
+        """<prefix>.markers.csv, .rows.csv, .windows.csv (with windows) and .trace.csv."""
+        L.check(L.lib().brr_session_summary_write(self.h, str(prefix).encode()), "summary_write")
+
+    def summary_end(self):
+        L.check(L.lib().brr_session_summary_end(self.h), "summary_end")
+
     # -- instrumentation ----------------------------------------------------------------
     def set_timing(self, on: bool):
         L.check(L.lib().brr_session_set_timing(self.h, 1 if on else 0), "set_timing")

@@ -270,6 +270,53 @@ int32_t brr_session_iteration(brr_session *s);
  * the full-size residual invariant eps = Y - mu - X beta - F alpha */
 int brr_session_linear_predictor(brr_session *s, double *out /* N */);
 
+/* posterior summaries accumulated on the device over kept sweeps (no reference counterpart): what
+ * users compute from the CSV rows, without the rows.  Folding a kept sweep in reads the state on
+ * the device (three small kernels on the session stream, no host synchronisation) and never
+ * changes the chain.
+ *   beta   per marker: Welford mean and centred sum of squares M2 of beta; per class k the sweeps
+ *          with comp == k (BayesR family; the Horseshoe has no classes)
+ *   g      per row: the same moments of the genetic value g_i = ((Y_i - mu) - eps_i) - sum_c
+ *          fixed[i,c] alpha_c (restart sessions, which hold no Y, use mu + X beta + eps of the state
+ *          at summary_begin)
+ *   window per window of `window` consecutive markers (window w = markers [w W, (w + 1) W), the last
+ *          one shorter; nW = ceil(M / W)): sweeps in which a marker of it is in the model (comp > 0;
+ *          Horseshoe: beta != 0), running means of its sum beta^2 and of its share of the sweep's
+ *          total sum beta^2 (0 in a sweep whose total is 0)
+ *   trace  one row of 12 + 2 G K doubles per kept sweep (Horseshoe: G = K = 1):
+ *          [iteration, mu, sigmaE, sigmaG, sigmaF, tau, eta, c2, sumsq_beta, var_g, h2, nnz], the
+ *          scalars as brr_session_get_scalar returns them then; count[g][k] = markers of group g in
+ *          class k (all markers; Horseshoe: M); ssq[g][k] = their sum beta^2.
+ *          var_g = sum (g_i - mean g)^2 / (N - 1), h2 = var_g / (var_g + sigmaE), nnz = markers in
+ *          the model.
+ * SD = sqrt(M2 / (n - 1)) (0 for n < 2 kept sweeps), PIP = 1 - count[m][0] / n, COMP_FREQ = count / n,
+ * WINDOW_PIP = count / n; the _M2 and _COUNT items are the raw accumulators (merging chains).
+ * Single-device sessions only: a column- or row-sharded session (shard_count > 1, row_shard_count
+ * > 1, brr_group members) is refused by summary_begin -- sharded summaries are out of scope. */
+enum brr_summary { BRR_SUM_BETA_MEAN = 0, BRR_SUM_BETA_SD, BRR_SUM_PIP, BRR_SUM_COMP_FREQ /* M x K row-major, fractions */,
+                   BRR_SUM_G_MEAN, BRR_SUM_G_SD, BRR_SUM_WINDOW_PIP, BRR_SUM_WINDOW_SSQ, BRR_SUM_WINDOW_SHARE,
+                   BRR_SUM_TRACE /* kept x width row-major */, BRR_SUM_BETA_M2, BRR_SUM_G_M2, BRR_SUM_COMP_COUNT, BRR_SUM_WINDOW_COUNT };
+/* allocate and zero the accumulators of an initialised session (a second begin resets them) */
+int     brr_session_summary_begin(brr_session *s, int32_t window /* markers per window, 0 = none */);
+/* fold the current state in; its trace row's iteration is the index of the latest finished sweep
+ * (brr_session_iteration() - 1) */
+int     brr_session_summary_accumulate(brr_session *s);
+/* the one-shots' loop without the CSV: iterations it = 0 .. max_iterations - 1, one sweep each, the
+ * state folded in when it >= burn_in && it % thinning == 0; 1 (and brr_last_error()) for the
+ * iteration settings the one-shots reject; a failing sweep's code is returned unchanged */
+int     brr_session_summary_run(brr_session *s, int32_t max_iterations, int32_t burn_in, int32_t thinning);
+int32_t brr_session_summary_count(brr_session *s);                /* kept sweeps so far */
+int32_t brr_session_summary_trace_width(brr_session *s);
+/* returns the item's length in doubles (out == NULL: only that), < 0 on error; synchronises */
+int64_t brr_session_summary_get(brr_session *s, int32_t which, double *out /* NULL = size */);
+/* <prefix>.markers.csv (marker, mean, sd, pip, freq_0 ..; Horseshoe: marker, mean, sd), .rows.csv
+ * (row, g_mean, g_sd), .windows.csv (with windows: first_marker, pip, ssq, share) and .trace.csv
+ * (named columns): one header line, %.17g values; marker and row indices are 0-based (global:
+ * col_offset + m).  The one-shot entry points write them when the environment variable
+ * BRR_SUMMARY_PREFIX is set (windows: BRR_SUMMARY_WINDOW markers, default 0). */
+int     brr_session_summary_write(brr_session *s, const char *prefix);
+int     brr_session_summary_end(brr_session *s);
+
 /* instrumentation: per-launch HIP-event timing of the streaming kernel (dots + residual
  * update), accumulated over the sweeps run while enabled. */
 int brr_session_set_timing(brr_session *s, int32_t on);
