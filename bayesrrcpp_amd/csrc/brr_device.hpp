@@ -54,7 +54,11 @@ struct Scal {
   double fx;   // row shards: this shard's part of a fixed-effect dot (BayesRv2Groups.cpp:220), summed across shards
   int lag_next;  // pipeline lag of the next fused sweep: 2 = Dev::lag, else 1 (set by k_hyper, see Dev::lag_thresh)
   int pad1;
-  unsigned long long n_slow;     // diagnostics: serial steps that needed the exact re-evaluation
+  unsigned long long n_slow;     // diagnostics: exact evaluations of the reference's decision (decide_bayesr) -- positions
+                                 // whose first decision of a sweep the fast softmax handed over (decide_pos: logL spread
+                                 // near the 700-guards, or p within 1e-12 of a cumulative sum), and serial chain steps
+                                 // decided exactly because that evaluation gave no window; the chains' windowed
+                                 // re-decisions are not counted
   unsigned long long n_changed;  // markers whose beta changed (session total)
   unsigned long long nch_mark;   // n_changed at the end of the previous sweep
   int prof_on;                   // diagnostics: k_solve phase timers on

@@ -639,10 +639,16 @@ __global__ __launch_bounds__(256) void k_encode_layout(Dev d, uint8_t *Xk) {
 // REFERENCE order: every column's class codes once, column-major (ldc bytes per column, the classes of
 // rows 4g .. 4g+3 in byte g, PLINK packing), so that each sweep's layout encoding is a gather of
 // contiguous bytes (k_encode_gather) instead of a pass over X (f32: 4 N P bytes) or over the 2-bit
-// tiles (16-B granules, one useful byte each).  Rows beyond N: class 0 (k_gram_int masks them).
+// tiles (16-B granules, one useful byte each).  Rows beyond N: class 0, also inside the last row quad --
+// k_gram_fp4 sums every row of its chunks and takes class 0 from the column totals, so a padding row (a
+// zero in X) must not be found in a class >= 1 whose value is 0 (a column with mean dosage exactly 1, or
+// with missing genotypes set to 0); k_gram_int masks the rows itself.
 __global__ __launch_bounds__(256) void k_xcls(Dev d, uint8_t *xcls) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= d.ldc) return;
+  // the quad's rows below N, two bits each
+  const int64_t left = d.N - 4 * g;
+  const uint32_t rows = left >= 4 ? 0xFFu : left > 0 ? (1u << (2 * (int)left)) - 1u : 0u;
   for (int64_t col = blockIdx.y; col < d.M; col += gridDim.y) {
     const int info = d.cls_info[col];
     uint32_t byte = 0;
@@ -662,7 +668,7 @@ __global__ __launch_bounds__(256) void k_xcls(Dev d, uint8_t *xcls) {
         byte = cl(x.x) | cl(x.y) << 2 | cl(x.z) << 4 | cl(x.w) << 6;
       }
     }
-    xcls[col * d.ldc + g] = (uint8_t)byte;
+    xcls[col * d.ldc + g] = (uint8_t)(byte & rows);
   }
 }
 
@@ -2021,6 +2027,7 @@ __device__ __forceinline__ FastDec decide_pos(const Dev &d, double r, const doub
                                               double sigmaE, double p, double x2, int m) {
   FastDec o = decide_fast(r, a, den, stride, d.K, sigmaE, p);
   if (o.ex) {
+    atomicAdd(&d.sc->n_slow, 1ull);  // diagnostics: this position's decision comes from the exact formula
     const int g = d.gAssign ? d.gAssign[m] : 0;
     Decision dc = decide_bayesr(r, x2, sigmaE, d.sigmaGG[g], d.pi + (int64_t)g * d.K, d.cva + g, d.G, d.K, p, true);
     if (dc.margin > 0.0) {

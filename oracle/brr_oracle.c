@@ -505,6 +505,7 @@ struct orc {
   double *deps;       /* shard_only: this shard's eps - eps_start */
   orc_rstream *rs;    /* r_compat stream (orc_set_rng_r), NULL = Philox */
   int seg;            /* shard_only: the exchange segment of the current sweep (n_exchanges) */
+  double regime[4];   /* ORC_V_REGIME: this sweep's 700-guard visit counts (diagnostics only) */
 };
 
 static double *dalloc(int64_t n) { return (double *)calloc((size_t)(n > 0 ? n : 1), sizeof(double)); }
@@ -743,9 +744,15 @@ static void bayesr_marker(orc *o, int64_t m, double *eps) {
   const double p = o->c.model == ORC_GROUPS ? orc_uniform(o->seed, ORC_T_MARKER, mg, (uint32_t)o->it, 0)
                                             : orc_beta11(o->seed, ORC_T_MARKER, mg, (uint32_t)o->it, 0);
   double acum;
-  int guard = 0;
+  int guard = 0, later = 0, chosen = 0;
   for (int i = 1; i < K; ++i) guard |= fabs(logL[i] - logL[0]) > 700.0;     /* :216 */
+  {
+    double lmax = logL[0], lmin = logL[0];
+    for (int i = 1; i < K; ++i) { lmax = fmax(lmax, logL[i]); lmin = fmin(lmin, logL[i]); }
+    if (lmax - lmin >= 600.0 && lmax - lmin < 800.0) o->regime[3] += 1.0;
+  }
   if (guard) {
+    o->regime[0] += 1.0;
     acum = 0.0;
   } else {
     double s = 0.0;
@@ -763,6 +770,7 @@ static void bayesr_marker(orc *o, int64_t m, double *eps) {
       }
       o->v[g * K + k] += 1.0;
       o->comp[m] = (double)k;
+      chosen = 1;
       break;
     } else if (k + 1 < K) {
       /* the reference evaluates logL[k+1] even at k = K-1 (one past the end); that value
@@ -774,8 +782,11 @@ static void bayesr_marker(orc *o, int64_t m, double *eps) {
         for (int i = 0; i < K; ++i) s += exp(logL[i] - logL[k + 1]);
         acum += 1.0 / s;
       }
+      later |= gk;
     }
   }
+  if (later) o->regime[1] += 1.0;
+  if (!chosen) o->regime[2] += 1.0;
   const double bn = o->beta[m];
   for (int64_t i = 0; i < N; ++i) eps[i] = yt[i] - x[i] * bn;                /* :243 */
 }
@@ -922,6 +933,7 @@ static void sweep_bayesr(orc *o) {
     if (c->model == ORC_GROUPS) fixed_effects(o);
     memset(o->v, 0, sizeof(double) * (size_t)(G * K));
     memset(o->betaAcum, 0, sizeof(double) * (size_t)G);
+    memset(o->regime, 0, sizeof(o->regime));
   }
   marker_pass(o);
   if (!last_seg(o)) {  /* an earlier exchange segment: nothing but the residual delta */
@@ -1113,6 +1125,7 @@ static double *vec_ptr(const orc *o, int which, int64_t *len) {
     case ORC_V_VCOUNT: *len = (int64_t)o->G * o->K; return o->v;
     case ORC_V_BETAACUM: *len = o->G; return o->betaAcum;
     case ORC_V_HSV: *len = o->P; return o->hsv;
+    case ORC_V_REGIME: *len = 4; return (double *)o->regime;
     default: *len = -1; return NULL;
   }
 }

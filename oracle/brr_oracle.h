@@ -109,7 +109,12 @@ enum {
 double orc_get_scalar(const orc *o, int which);
 enum {
   ORC_V_BETA = 0, ORC_V_COMP, ORC_V_EPS, ORC_V_SIGMAGG, ORC_V_PI, ORC_V_ALPHA,
-  ORC_V_LAMBDA, ORC_V_XSQ, ORC_V_ORDER, ORC_V_VCOUNT, ORC_V_BETAACUM, ORC_V_HSV
+  ORC_V_LAMBDA, ORC_V_XSQ, ORC_V_ORDER, ORC_V_VCOUNT, ORC_V_BETAACUM, ORC_V_HSV,
+  /* 700-guard regime of the latest sweep's BayesR marker visits (BayesRv2.cpp:216-242), counted by
+   * this process, reset at each sweep, read by nothing in the sampler: [visits whose first guard
+   * (against logL[0]) is true, visits with a later guard (against logL[k+1]) true, visits that
+   * select no component, visits with max logL - min logL in [600, 800)] */
+  ORC_V_REGIME
 };
 int64_t orc_get_vector(const orc *o, int which, double *out); /* returns length; out may be NULL */
 /* overwrite state (for forced-state parity tests) */

@@ -21,7 +21,9 @@ ORDER_BLOCKED, ORDER_REFERENCE, ORDER_IDENTITY = 0, 1, 2
 
 (S_MU, S_SIGMAE, S_SIGMAG, S_SIGMAF, S_TAU, S_ETA, S_C2, S_SUMSQ_BETA) = range(8)
 (V_BETA, V_COMP, V_EPS, V_SIGMAGG, V_PI, V_ALPHA, V_LAMBDA, V_XSQ, V_ORDER, V_VCOUNT,
- V_BETAACUM, V_HSV) = range(12)
+ V_BETAACUM, V_HSV, V_REGIME) = range(13)
+# V_REGIME entries: marker visits of the latest sweep in the 700-guard regime (brr_oracle.h)
+R_GUARD0, R_GUARD_LATER, R_NO_SELECTION, R_SPREAD_600_800 = range(4)
 
 T_MARKER, T_MU, T_SIGMAE, T_SIGMAG, T_PI = 1, 2, 3, 4, 5
 T_INIT = 13

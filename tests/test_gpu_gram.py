@@ -138,7 +138,16 @@ def test_reference_order_fp4_gram_is_correctly_rounded(brr, require_gpu, storage
     Y = rng.standard_normal(N)
     s = _ref_session(brr, L, X, Y, B, L.X_2BIT if storage == "2bit" else L.X_F32)
     assert int(s.scalar(GRAM_NP)) == nclass - 1
+    _check_reference_layout(s, L, X, B)
+    s.close()
+
+
+def _check_reference_layout(s, L, X, B):
+    """First and last diagonal and cross-Gram block of the sweep's layout, and every column's xsq (the
+    diagonal of every block at init), against the exact sums: after init and after a sweep's re-layout"""
+    P = X.shape[1]
     nb = (P + B - 1) // B
+    assert np.array_equal(s.vector(L.XSQ), np.array([math.fsum(X[:, j].astype(np.float64) ** 2) for j in range(P)]))
     for stage in range(2):
         if stage:
             s.sweep(1)
@@ -152,6 +161,29 @@ def test_reference_order_fp4_gram_is_correctly_rounded(brr, require_gpu, storage
             assert np.array_equal(G[b][: len(ca), : len(ca)], ge), f"stage {stage} gram block {b}"
             xge = _exact_block(X, ca, cb)
             assert np.array_equal(XG[b][: len(ca), : len(cb)], xge), f"stage {stage} cross-Gram block {b}"
+
+
+@pytest.mark.parametrize("storage", ["f32", "2bit"])
+@pytest.mark.parametrize("N", [257, 518, 1003])  # 1, 2 and 3 rows in the last row quad
+def test_reference_order_fp4_gram_zero_valued_class(brr, require_gpu, storage, N):
+    """Columns whose middle or highest class value is exactly 0 (mean dosage exactly 1; missing genotypes
+    set to the mean) with N no multiple of 4: the rows that pad the last row quad hold zeros, and
+    k_gram_fp4 -- which sums every row it reads and takes the lowest class from the column totals -- must
+    not find them in the zero-valued class.  (Found by the guard cohort of tests/guard_cases.py: two such
+    columns at 257 x 333, xsq 2.3 % off, the REFERENCE-order chain off the oracle in its first sweep.)"""
+    from bayesrrcpp_amd import _lib as L
+    rng = np.random.default_rng(N)
+    B = 128
+    P = 3 * B - 37
+    X = _genotypes(rng, N, P, 3)
+    for j in range(0, P, 7):  # (-a, 0, a) and (-a, -a / 2, 0), in every block
+        g = rng.integers(0, 3, N)
+        g[:3] = [0, 1, 2]
+        X[:, j] = (g - (1 if j % 2 else 2)).astype(np.float32) * np.float32(0.5 + j / P)
+    Y = rng.standard_normal(N)
+    s = _ref_session(brr, L, X, Y, B, L.X_2BIT if storage == "2bit" else L.X_F32)
+    assert int(s.scalar(GRAM_NP)) == 2
+    _check_reference_layout(s, L, X, B)
     s.close()
 
 
