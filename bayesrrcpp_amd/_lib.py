@@ -25,6 +25,12 @@ SUM_CLASS_ITEMS = (SUM_PIP, SUM_COMP_FREQ, SUM_COMP_COUNT)                      
 SUM_WINDOW_ITEMS = (SUM_WINDOW_PIP, SUM_WINDOW_SSQ, SUM_WINDOW_SHARE, SUM_WINDOW_COUNT)  # window > 0 only
 TRACE_HEADER = ("iteration", "mu", "sigmaE", "sigmaG", "sigmaF", "tau", "eta", "c2", "sumsq_beta", "var_g",
                 "h2", "nnz")
+# brr_predict: out-of-sample prediction (brr_session_predict_get)
+(PRED_G_MEAN, PRED_G_SD, PRED_G_M2, PRED_TRACE) = range(4)
+PRED_NAMES = ("g_mean", "g_sd", "g_m2", "trace")
+PRED_TRACE_HEADER = ("iteration", "mean_g", "var_g", "mean_y", "var_y", "cov_yg", "cor_yg", "mse")
+PREDICT_CHUNK = 2048     # markers per chunk of the score's summation order (brr_predict_chunk())
+PREDICT_ROW_TILE = 4096  # rows of a score workgroup on 2-bit codes (brr_predict_row_tile(); f32: a quarter)
 ABI_VERSION = 4
 
 LOG_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
@@ -67,6 +73,12 @@ EXPORTED = [
     "brr_session_summary_begin", "brr_session_summary_accumulate", "brr_session_summary_run",
     "brr_session_summary_count", "brr_session_summary_trace_width", "brr_session_summary_get",
     "brr_session_summary_write", "brr_session_summary_end",
+    "brr_predict_chunk", "brr_predict_row_tile", "brr_session_predict_upload_bed",
+    "brr_session_predict_upload_x_f64", "brr_session_predict_upload_x_f32", "brr_session_predict_detach",
+    "brr_session_predict_rows", "brr_session_predict_set_y", "brr_session_predict_score",
+    "brr_session_predict_begin", "brr_session_predict_accumulate", "brr_session_predict_run",
+    "brr_session_predict_count", "brr_session_predict_get", "brr_session_predict_write",
+    "brr_session_predict_end", "brr_session_predict_timing",
 ]
 
 _lib = None
@@ -168,6 +180,27 @@ def lib():
     L.brr_session_summary_get.argtypes = [vp, C.c_int32, D]
     L.brr_session_summary_write.argtypes = [vp, C.c_char_p]
     L.brr_session_summary_end.argtypes = [vp]
+    L.brr_predict_chunk.restype = C.c_int32
+    L.brr_predict_row_tile.restype = C.c_int32
+    L.brr_session_predict_upload_bed.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64, C.c_int64,
+                                                 C.POINTER(C.c_float)]
+    L.brr_session_predict_upload_x_f64.argtypes = [vp, D, C.c_int64, C.c_int64]
+    L.brr_session_predict_upload_x_f32.argtypes = [vp, C.POINTER(C.c_float), C.c_int64, C.c_int64]
+    L.brr_session_predict_detach.argtypes = [vp]
+    L.brr_session_predict_rows.restype = C.c_int64
+    L.brr_session_predict_rows.argtypes = [vp]
+    L.brr_session_predict_set_y.argtypes = [vp, D]
+    L.brr_session_predict_score.argtypes = [vp, D, D]
+    L.brr_session_predict_begin.argtypes = [vp]
+    L.brr_session_predict_accumulate.argtypes = [vp]
+    L.brr_session_predict_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.brr_session_predict_count.restype = C.c_int32
+    L.brr_session_predict_count.argtypes = [vp]
+    L.brr_session_predict_get.restype = C.c_int64
+    L.brr_session_predict_get.argtypes = [vp, C.c_int32, D]
+    L.brr_session_predict_write.argtypes = [vp, C.c_char_p]
+    L.brr_session_predict_end.argtypes = [vp]
+    L.brr_session_predict_timing.argtypes = [vp, D, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

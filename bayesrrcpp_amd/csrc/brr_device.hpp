@@ -195,4 +195,30 @@ struct SumDev {
   int64_t nW;               // ceil(M / W)
 };
 
+// Out-of-sample prediction (brr_predict.hpp, brr_session_predict_*): a target cohort of N2 rows for
+// the session's M markers, its scores g2 = X2 beta and their accumulators, by value to k_predict_*.
+//   codes    2-bit target storage: column j at codes + j ldc, PLINK packing (row i in bits 2(i&3).. of
+//            byte i>>2), ldc a multiple of 64 bytes; table f32 [M][4] the value of each code
+//   X        f32 target storage: column-major, ld a multiple of 64 rows, zero rows beyond N2
+//   part     f64 [nchunk][NP] the chunk partial sums of k_predict_score (NP = N2 rounded up to 16)
+//   g        f64 [NP] the scores of the latest pass (the chunk partials left-folded)
+//   rslab    f64 [cdiv(N2, 256)][PRED_SLAB] per-workgroup moments of k_predict_rows
+//   row      f64 [PRED_WIDTH] the fold's trace row; cnt: its last-arriver ticket
+constexpr int PRED_CHUNK = 2048;  // markers per chunk: the unit of the summation order
+constexpr int PRED_ROWS = 4096;   // rows per k_predict_score workgroup on 2-bit codes (f32: PRED_ROWS / 4)
+constexpr int PRED_WIDTH = 8;     // [iteration, mean_g, var_g, mean_y, var_y, cov_yg, cor_yg, mse]
+constexpr int PRED_SLAB = 7;      // rows, mean g, M2 g, mean y, M2 y, co-moment, sum (y - mu - g)^2
+struct PredDev {
+  const uint8_t *codes;
+  const float *table;
+  const float *X;
+  int64_t N2, ldc, ld, NP, M;
+  int nchunk;
+  double *part, *g;
+  const double *Y2;         // [N2] validation phenotypes, or nullptr
+  double *gmean, *gM2;      // [N2] Welford mean / centred sum of squares of g2 (between begin and end)
+  double *rslab, *row;
+  int *cnt;
+};
+
 }  // namespace brr

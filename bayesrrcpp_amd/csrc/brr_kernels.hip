@@ -5078,6 +5078,10 @@ __global__ __launch_bounds__(256) void k_linpred(Dev d, double *out) {
 // Posterior summaries over kept sweeps (k_summary_*)
 #include "brr_summary.hpp"
 
+// ------------------------------------------------------------------------------------
+// Out-of-sample prediction: a target cohort scored on the device (k_predict_*)
+#include "brr_predict.hpp"
+
 }  // namespace brr
 
 // ======================================================================================
@@ -5609,6 +5613,30 @@ hipError_t launch_summary(const Dev &d, const SumDev &q, int n, int iteration, h
 hipError_t launch_summary_yrec(const Dev &d, double *y, hipStream_t st) {
   hipLaunchKernelGGL(k_linpred, dim3(cdiv64(d.N, 256)), dim3(256), 0, st, d, y);
   hipLaunchKernelGGL(k_summary_yrec, dim3(cdiv64(d.N, 256)), dim3(256), 0, st, d, y);
+  return hipGetLastError();
+}
+
+// g2 = X2 beta of the attached target cohort (brr_predict.hpp) into p.part / p.g
+hipError_t launch_predict_score(const PredDev &p, const Dev &d, const double *beta, hipStream_t st) {
+  if (p.codes)
+    hipLaunchKernelGGL(k_predict_score<true>, dim3(cdiv64(p.NP, PredTile<true>::ROWS), (unsigned)p.nchunk), dim3(256), 0, st,
+                       p, beta);
+  else
+    hipLaunchKernelGGL(k_predict_score<false>, dim3(cdiv64(p.NP, PredTile<false>::ROWS), (unsigned)p.nchunk), dim3(256), 0,
+                       st, p, beta);
+  hipLaunchKernelGGL(k_predict_rows<false>, dim3(cdiv64(p.N2, 256)), dim3(256), 0, st, p, d, 0.0, 0.0);
+  return hipGetLastError();
+}
+
+// the chain's current beta scored and folded in as kept sweep number n (1-based)
+hipError_t launch_predict_fold(const PredDev &p, const Dev &d, int n, int iteration, hipStream_t st) {
+  if (p.codes)
+    hipLaunchKernelGGL(k_predict_score<true>, dim3(cdiv64(p.NP, PredTile<true>::ROWS), (unsigned)p.nchunk), dim3(256), 0, st,
+                       p, d.beta);
+  else
+    hipLaunchKernelGGL(k_predict_score<false>, dim3(cdiv64(p.NP, PredTile<false>::ROWS), (unsigned)p.nchunk), dim3(256), 0,
+                       st, p, d.beta);
+  hipLaunchKernelGGL(k_predict_rows<true>, dim3(cdiv64(p.N2, 256)), dim3(256), 0, st, p, d, (double)n, (double)iteration);
   return hipGetLastError();
 }
 

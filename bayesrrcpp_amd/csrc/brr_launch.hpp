@@ -66,6 +66,10 @@ hipError_t launch_markers(const Dev &d, int mode, uint32_t it, hipStream_t st);
 // posterior summaries (brr_summary.hpp): kept sweep number n (1-based) folded into q's accumulators
 hipError_t launch_summary(const Dev &d, const SumDev &q, int n, int iteration, hipStream_t st);
 hipError_t launch_summary_yrec(const Dev &d, double *y, hipStream_t st);  // y = mu + X beta + F alpha + eps
+// out-of-sample prediction (brr_predict.hpp): the target cohort's scores for a device beta of M doubles
+// (into p.part / p.g), and the chain's current beta scored and folded in as kept sweep number n
+hipError_t launch_predict_score(const PredDev &p, const Dev &d, const double *beta, hipStream_t st);
+hipError_t launch_predict_fold(const PredDev &p, const Dev &d, int n, int iteration, hipStream_t st);
 hipError_t launch_hyper(const Dev &d, uint32_t it, const double *stats, hipStream_t st);
 hipError_t launch_hyper_init(const Dev &d, const double *stats, bool pi_given, hipStream_t st);
 

@@ -42,6 +42,9 @@ int session_sweep(brr_session *s, int n, bool check);
 // posterior summaries (brr_session_summary_*): the current state folded in as kept sweep `iteration`
 // of the caller's loop (brr_session_summary_accumulate records the session's own sweep counter)
 int summary_fold(brr_session *s, int iteration);
+// summary_run's and predict_run's loop: a sweep per iteration, every active accumulator (summary,
+// prediction) folded at the kept ones; `what` names the caller in messages
+int run_folding(brr_session *s, const char *what, int max_iterations, int burn_in, int thinning);
 
 // a caller's options over the defaults, by the caller's ABI version: an older caller's struct
 // ends before the fields a later ABI added (ABI 1: row shards, ABI 2: exchanges_per_sweep)

@@ -159,6 +159,53 @@ struct Summary {
   }
 };
 
+// out-of-sample prediction (brr_session_predict_*, brr_predict.hpp): the attached target cohort
+// (between an upload and detach) and, between predict_begin and predict_end, its accumulators.  The
+// device buffers are its own (not in brr_session::allocs).
+struct Predict {
+  static constexpr int RING = 64;  // pinned trace rows in flight before a fold has to synchronise
+  PredDev p{};
+  double *beta_tmp = nullptr;  // [M] a caller's beta on the device (predict_score)
+  double *y2 = nullptr;        // [N2] validation phenotypes (p.Y2 once set)
+  bool active = false;         // between predict_begin and predict_end
+  int n = 0;                   // kept sweeps folded in
+  double *pin = nullptr;       // [RING][PRED_WIDTH] pinned copies of the device trace row
+  int pending = 0;             // rows copied into pin (asynchronously) and not yet appended
+  std::vector<double> trace;   // [n - pending][PRED_WIDTH]
+  std::vector<void *> allocs;      // the target's buffers
+  std::vector<void *> acc_allocs;  // the accumulators'
+  // instrumentation (brr_session_set_timing): an event pair around each fold's kernels, and the total
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  double t_fold = 0;
+  int64_t n_fold = 0;
+  void release_acc() {
+    for (void *q : acc_allocs) (void)hipFree(q);
+    acc_allocs.clear();
+    for (auto &e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    ev.clear();
+    t_fold = 0;
+    n_fold = 0;
+    if (pin) (void)hipHostFree(pin);
+    pin = nullptr;
+    p.gmean = p.gM2 = p.rslab = p.row = nullptr;
+    p.cnt = nullptr;
+    active = false;
+    n = pending = 0;
+    trace.clear();
+  }
+  void release() {
+    release_acc();
+    for (void *q : allocs) (void)hipFree(q);
+    allocs.clear();
+  }
+  // the stream has been synchronised: every pending row has landed
+  void drain() {
+    for (int i = 0; i < pending; ++i)
+      trace.insert(trace.end(), pin + (size_t)i * PRED_WIDTH, pin + (size_t)(i + 1) * PRED_WIDTH);
+    pending = 0;
+  }
+};
+
 struct brr_session {
   brr_options opt;
   Logger log;
@@ -221,6 +268,10 @@ struct brr_session {
   std::vector<void *> allocs;
   SampleRing ring;
   Summary *sum = nullptr;  // between summary_begin and summary_end
+  Predict *pred = nullptr;  // between a predict_upload and predict_detach
+  // training came from a .bed: the value table of its columns ([M][4] f32), kept for a target cohort
+  // attached with table = NULL (2-bit storage: Dev::xlut itself; f32 storage: a buffer in allocs)
+  const float *bed_table = nullptr;
   bool in_group = false;   // member of a brr_group
 
   bool alloc_failed = false;  // after one failed allocation the rest are not attempted
@@ -247,6 +298,7 @@ struct brr_session {
     if (st) (void)hipStreamSynchronize(st);
     brr::sample_ring_close(this);
     if (sum) { sum->release(); delete sum; }
+    if (pred) { pred->release(); delete pred; }
     if (comm) (void)ncclCommDestroy(comm);
     for (void *p : allocs) (void)hipFree(p);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
@@ -397,6 +449,7 @@ int upload_order(brr_session *s, const std::vector<int32_t> &order) {
 int check_device_error(brr_session *s, bool mid_sweep = false) {
   HIPCHK(hipStreamSynchronize(s->st));
   if (s->sum) s->sum->drain();  // the summary's trace rows copied so far have landed
+  if (s->pred) s->pred->drain();
   std::vector<int> sy(SY_WORDS);
   HIPCHK(hipMemcpy(sy.data(), s->d.sync, sizeof(int) * SY_WORDS, hipMemcpyDeviceToHost));
   if (sy[SY_ERR]) {
@@ -1510,6 +1563,7 @@ static int upload_x_any(brr_session *s, const void *X, bool f64, int64_t ldx) {
   if (!s || !X) { set_error("null argument"); return -1; }
   if (ldx < s->N) { set_error("ldx < N"); return -1; }
   HIPCHK(hipSetDevice(s->device));
+  s->bed_table = nullptr;  // the columns no longer come from a .bed
   if (s->x2bit) {
     const int64_t ldc = s->d.ldc;
     const int64_t chunk_cols = std::max<int64_t>(1, std::min<int64_t>(s->M, (int64_t)(256ll << 20) / ldc));
@@ -1584,6 +1638,14 @@ int brr_session_upload_bed(brr_session *s, const uint8_t *bed, int64_t bytes_per
     xf.resize((size_t)(s->d.ld * chunk_cols));
   }
   struct Free { uint8_t *p; ~Free() { if (p) (void)hipFree(p); } } free_stage{stage};
+  // the columns' value table stays on the device for brr_session_predict_upload_bed(table = NULL)
+  float *keep = nullptr;
+  if (!s->x2bit) {
+    for (void *q : s->allocs)
+      if (q == (const void *)s->bed_table) keep = const_cast<float *>(s->bed_table);  // a second upload reuses it
+    if (!keep && s->alloc(&keep, 4 * s->M)) return -2;
+  }
+  s->bed_table = nullptr;
   static const double gval[4] = {2.0, 0.0 /* missing */, 1.0, 0.0};
   for (int64_t c0 = 0; c0 < s->M; c0 += chunk_cols) {
     const int64_t nc = std::min<int64_t>(chunk_cols, s->M - c0);
@@ -1619,8 +1681,10 @@ int brr_session_upload_bed(brr_session *s, const uint8_t *bed, int64_t bytes_per
     } else {
       HIPCHK(hipMemcpy(const_cast<float *>(s->d.X) + s->d.ld * c0, xf.data(), sizeof(float) * s->d.ld * nc,
                        hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(keep + 4 * c0, lut.data(), sizeof(float) * 4 * nc, hipMemcpyHostToDevice));
     }
   }
+  s->bed_table = s->x2bit ? s->d.xlut : keep;
   s->have_x = true;
   return 0;
 }
@@ -1629,6 +1693,7 @@ int brr_session_synthesize(brr_session *s, uint64_t ds, double h2, int64_t n_cau
   if (!s) return -1;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(launch_synth_x(s->d, ds, s->st));
+  s->bed_table = nullptr;
   s->have_x = true;
   // this shard's genetic values X_c beta_c over its causal columns
   if (n_causal < 1) n_causal = std::max<int64_t>(1, std::min<int64_t>(1000, s->M_total / 10));
@@ -2213,6 +2278,7 @@ int brr_session_synchronize(brr_session *s) {
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->st));
   if (s->sum) s->sum->drain();
+  if (s->pred) s->pred->drain();
   return 0;
 }
 
@@ -2359,20 +2425,7 @@ int brr_session_summary_accumulate(brr_session *s) {
 
 int brr_session_summary_run(brr_session *s, int32_t max_iterations, int32_t burn_in, int32_t thinning) {
   if (!summary_of(s, "summary_run")) return -1;
-  if (max_iterations < burn_in || max_iterations < 1 || burn_in < 1 || thinning < 1) {  // the one-shots' rule
-    set_error("summary_run: burn_in has to be a positive integer and smaller than the maximum number of "
-              "iterations, thinning positive (max_iterations %d, burn_in %d, thinning %d)",
-              (int)max_iterations, (int)burn_in, (int)thinning);
-    return 1;
-  }
-  for (int it = 0; it < max_iterations; ++it) {
-    // the device check every 16 iterations and at the end, as the one-shots' loop
-    const bool check = (it & 15) == 15 || it + 1 == max_iterations;
-    if (int rc = brr::session_sweep(s, 1, check)) return rc;
-    if (it >= burn_in && it % thinning == 0)
-      if (int rc = brr::summary_fold(s, it)) return rc;
-  }
-  return summary_sync(s);
+  return brr::run_folding(s, "summary_run", max_iterations, burn_in, thinning);  // (with brr_session_predict_run)
 }
 
 int32_t brr_session_summary_count(brr_session *s) {
@@ -2541,6 +2594,447 @@ int brr_session_summary_end(brr_session *s) {
   summary_drop(s);
   return 0;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// Out-of-sample prediction: a target cohort scored on the device (include/brr.h; kernels in
+// brr_predict.hpp)
+namespace {
+
+Predict *predict_of(brr_session *s, const char *what, bool need_begin) {
+  if (!s) { set_error("%s: null session", what); return nullptr; }
+  if (!s->pred) {
+    set_error("%s: no target cohort attached (brr_session_predict_upload_bed / _upload_x first)", what);
+    return nullptr;
+  }
+  if (need_begin && !s->pred->active) {
+    set_error("%s: no prediction accumulators (brr_session_predict_begin first)", what);
+    return nullptr;
+  }
+  return s->pred;
+}
+
+void predict_drop(brr_session *s) {
+  if (!s->pred) return;
+  (void)hipSetDevice(s->device);
+  (void)hipStreamSynchronize(s->st);  // no fold may still use the buffers
+  s->pred->release();
+  delete s->pred;
+  s->pred = nullptr;
+}
+
+int predict_sync(brr_session *s) {
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->st));
+  if (s->sum) s->sum->drain();
+  s->pred->drain();
+  return 0;
+}
+
+// The checks and allocations every attach shares: the session takes a target of N2 rows in 2-bit
+// (bits2) or f32 storage, replacing an attached one.  The byte size is formed in 128-bit arithmetic
+// and compared with the device's free memory before anything is allocated.
+int predict_attach(brr_session *s, const char *what, int64_t N2, bool bits2) {
+  if (s->nshard > 1 || s->nrshard > 1 || s->in_group) {
+    set_error("%s: prediction on column- or row-sharded sessions is not supported "
+              "(shard_count %d, row_shard_count %d%s)", what, s->nshard, s->nrshard,
+              s->in_group ? ", brr_group member" : "");
+    return -1;
+  }
+  if (N2 < 1) { set_error("%s: N2 %lld < 1", what, (long long)N2); return -1; }
+  const int64_t M = s->M;
+  const int64_t nchunk = (M + PRED_CHUNK - 1) / PRED_CHUNK;
+  if (nchunk > 65535) { set_error("%s: M %lld exceeds %d markers", what, (long long)M, 65535 * PRED_CHUNK); return -1; }
+  if (N2 > (int64_t)1 << 48) { set_error("%s: N2 %lld exceeds 2^48 rows", what, (long long)N2); return -1; }
+  HIPCHK(hipSetDevice(s->device));
+  predict_drop(s);
+  typedef unsigned __int128 u128;
+  const int64_t ldc = ((N2 + 3) / 4 + 63) / 64 * 64;  // bytes per code column
+  const int64_t ld = (N2 + 63) / 64 * 64;             // rows per f32 column
+  const int64_t NP = (N2 + 15) / 16 * 16;
+  const u128 storage = bits2 ? (u128)ldc * (u128)M + (u128)16 * (u128)M : (u128)4 * (u128)ld * (u128)M;
+  const u128 need = storage + (u128)8 * (u128)nchunk * (u128)NP + (u128)8 * (u128)NP + (u128)8 * (u128)N2 +
+                    (u128)8 * (u128)M;
+  size_t freeb = 0, totalb = 0;
+  HIPCHK(hipMemGetInfo(&freeb, &totalb));
+  if (need > (u128)freeb) {
+    set_error("%s: the target cohort does not fit: %.0f bytes needed (N2 %lld rows x M %lld markers, %s storage, "
+              "%.0f bytes of genotypes), %lld bytes free of %lld", what, (double)need, (long long)N2, (long long)M,
+              bits2 ? "2-bit" : "f32", (double)storage, (long long)freeb, (long long)totalb);
+    return -2;
+  }
+  Predict *u = new Predict();
+  PredDev &p = u->p;
+  p.N2 = N2; p.ldc = ldc; p.ld = ld; p.NP = NP; p.M = M; p.nchunk = (int)nchunk;
+  int rc = 0;
+  auto take = [&](auto **q, int64_t n) {
+    if (rc) { *q = nullptr; return; }
+    rc = dalloc(q, n);
+    if (!rc) u->allocs.push_back((void *)*q);
+  };
+  if (bits2) {
+    take(const_cast<uint8_t **>(&p.codes), ldc * M);
+    take(const_cast<float **>(&p.table), 4 * M);
+  } else {
+    take(const_cast<float **>(&p.X), ld * M);
+  }
+  take(&p.part, nchunk * NP);
+  take(&p.g, NP);
+  take(&u->y2, N2);
+  take(&u->beta_tmp, M);
+  if (rc) {
+    const std::string why = brr_last_error();
+    u->release();
+    delete u;
+    set_error("%s: the target cohort does not fit (%.0f bytes: N2 %lld, M %lld): %s", what, (double)need, (long long)N2,
+              (long long)M, why.c_str());
+    return -2;
+  }
+  s->pred = u;
+  return 0;
+}
+
+// an attach that failed half way leaves no target
+int predict_fail(brr_session *s, int rc) {
+  const std::string why = brr_last_error();
+  (void)hipGetLastError();
+  predict_drop(s);
+  set_error("%s", why.c_str());
+  return rc;
+}
+
+int predict_upload_x_any(brr_session *s, const void *X2, bool f64, int64_t N2, int64_t ldx) {
+  const char *what = f64 ? "predict_upload_x_f64" : "predict_upload_x_f32";
+  if (!s || !X2) { set_error("%s: null argument", what); return -1; }
+  if (ldx < N2) { set_error("%s: ldx < N2", what); return -1; }
+  if (int rc = predict_attach(s, what, N2, false)) return rc;
+  const PredDev &p = s->pred->p;
+  const size_t esz = f64 ? 8 : 4;
+  const int64_t chunk_cols = std::min<int64_t>(
+      65535, std::max<int64_t>(1, (int64_t)(256ll << 20) / (int64_t)(esz * ldx)));  // grid.y limit
+  void *stage = nullptr;
+  if (hipMalloc(&stage, esz * (size_t)ldx * (size_t)std::min<int64_t>(chunk_cols, s->M)) != hipSuccess) {
+    set_error("%s: no device memory for the staging buffer", what);
+    return predict_fail(s, -2);
+  }
+  for (int64_t c0 = 0; c0 < s->M; c0 += chunk_cols) {
+    const int64_t nc = std::min<int64_t>(chunk_cols, s->M - c0);
+    hipError_t e = hipMemcpy(stage, (const char *)X2 + esz * (size_t)ldx * (size_t)c0, esz * (size_t)ldx * (size_t)nc,
+                             hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+      e = launch_cast_x(stage, f64, ldx, const_cast<float *>(p.X) + p.ld * c0, p.ld, N2, nc, s->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->st);
+    if (e != hipSuccess) {
+      (void)hipFree(stage);
+      set_error("%s: upload failed: %s", what, hipGetErrorString(e));
+      return predict_fail(s, -2);
+    }
+  }
+  (void)hipFree(stage);
+  return 0;
+}
+
+const char *kPredictNames[] = {"G_MEAN", "G_SD", "G_M2", "TRACE"};
+
+// the current state folded in as kept sweep `iteration` of the caller's loop
+int predict_fold(brr_session *s, int iteration) {
+  Predict *u = predict_of(s, "predict_accumulate", true);
+  if (!u) return -1;
+  HIPCHK(hipSetDevice(s->device));
+  if (u->pending == Predict::RING)  // every pinned row is in flight: the one place a fold waits
+    if (int rc = predict_sync(s)) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (s->timing) {
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    u->ev.emplace_back(e0, e1);
+    HIPCHK(hipEventRecord(e0, s->st));
+  }
+  HIPCHK(launch_predict_fold(u->p, s->d, u->n + 1, iteration, s->st));
+  if (s->timing) HIPCHK(hipEventRecord(e1, s->st));
+  HIPCHK(hipMemcpyAsync(u->pin + (size_t)u->pending * PRED_WIDTH, u->p.row, sizeof(double) * PRED_WIDTH,
+                        hipMemcpyDeviceToHost, s->st));
+  u->n++;
+  u->pending++;
+  return 0;
+}
+
+}  // namespace
+
+// The one-shots' loop without the CSV, shared by summary_run and predict_run: iterations it = 0 ..
+// max_iterations - 1, one sweep each; at a kept one every active accumulator (summary, prediction or
+// both) folds the state in, so one chain yields both.
+int brr::run_folding(brr_session *s, const char *what, int max_iterations, int burn_in, int thinning) {
+  if (max_iterations < burn_in || max_iterations < 1 || burn_in < 1 || thinning < 1) {  // the one-shots' rule
+    set_error("%s: burn_in has to be a positive integer and smaller than the maximum number of "
+              "iterations, thinning positive (max_iterations %d, burn_in %d, thinning %d)",
+              what, max_iterations, burn_in, thinning);
+    return 1;
+  }
+  for (int it = 0; it < max_iterations; ++it) {
+    // the device check every 16 iterations and at the end, as the one-shots' loop
+    const bool check = (it & 15) == 15 || it + 1 == max_iterations;
+    if (int rc = brr::session_sweep(s, 1, check)) return rc;
+    if (it >= burn_in && it % thinning == 0) {
+      if (s->sum)
+        if (int rc = brr::summary_fold(s, it)) return rc;
+      if (s->pred && s->pred->active)
+        if (int rc = predict_fold(s, it)) return rc;
+    }
+  }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->st));
+  if (s->sum) s->sum->drain();
+  if (s->pred) s->pred->drain();
+  return 0;
+}
+
+extern "C" {
+
+int brr_session_predict_upload_bed(brr_session *s, const uint8_t *bed, int64_t N2, int64_t bytes_per_col,
+                                   const float *table) {
+  const char *what = "predict_upload_bed";
+  if (!s || !bed) { set_error("%s: null argument", what); return -1; }
+  const int64_t nbytes = N2 < 1 ? 0 : (N2 + 3) / 4;
+  if (N2 >= 1 && bytes_per_col < nbytes) { set_error("%s: bytes_per_col < ceil(N2/4)", what); return -1; }
+  if (!table && !s->bed_table) {
+    set_error("%s: table = NULL takes the training cohort's value table, but the training genotypes did not "
+              "come from a .bed (brr_session_upload_bed): pass the target's table", what);
+    return -1;
+  }
+  if (int rc = predict_attach(s, what, N2, true)) return rc;
+  const PredDev &p = s->pred->p;
+  const int64_t ldc = p.ldc, M = s->M;
+  const int64_t chunk_cols = std::max<int64_t>(1, std::min<int64_t>(M, (int64_t)(64ll << 20) / ldc));
+  std::vector<uint8_t> codes((size_t)(ldc * chunk_cols));
+  for (int64_t c0 = 0; c0 < M; c0 += chunk_cols) {
+    const int64_t nc = std::min<int64_t>(chunk_cols, M - c0);
+    for (int64_t j = 0; j < nc; ++j) {
+      uint8_t *dst = &codes[(size_t)(ldc * j)];
+      std::memcpy(dst, bed + bytes_per_col * (c0 + j), (size_t)nbytes);
+      // rows >= N2 of the last byte and the padding: code 01 (missing), whatever the caller left there
+      if (N2 & 3) dst[nbytes - 1] = (uint8_t)((dst[nbytes - 1] & ((1u << (2 * (N2 & 3))) - 1u)) |
+                                              (0x55u & ~((1u << (2 * (N2 & 3))) - 1u)));
+      std::memset(dst + nbytes, 0x55, (size_t)(ldc - nbytes));
+    }
+    if (hipMemcpy(const_cast<uint8_t *>(p.codes) + ldc * c0, codes.data(), (size_t)(ldc * nc), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+      set_error("%s: upload failed: %s", what, hipGetErrorString(hipGetLastError()));
+      return predict_fail(s, -2);
+    }
+  }
+  if (hipMemcpy(const_cast<float *>(p.table), table ? table : s->bed_table, sizeof(float) * 4 * (size_t)M,
+                table ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != hipSuccess) {
+    set_error("%s: table upload failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return predict_fail(s, -2);
+  }
+  return 0;
+}
+
+int brr_session_predict_upload_x_f64(brr_session *s, const double *X2, int64_t N2, int64_t ldx) {
+  return predict_upload_x_any(s, X2, true, N2, ldx);
+}
+int brr_session_predict_upload_x_f32(brr_session *s, const float *X2, int64_t N2, int64_t ldx) {
+  return predict_upload_x_any(s, X2, false, N2, ldx);
+}
+
+int brr_session_predict_detach(brr_session *s) {
+  if (!predict_of(s, "predict_detach", false)) return -1;
+  predict_drop(s);
+  return 0;
+}
+
+int64_t brr_session_predict_rows(brr_session *s) {
+  Predict *u = predict_of(s, "predict_rows", false);
+  return u ? u->p.N2 : -1;
+}
+
+int brr_session_predict_set_y(brr_session *s, const double *Y2) {
+  Predict *u = predict_of(s, "predict_set_y", false);
+  if (!u) return -1;
+  if (!Y2) { set_error("predict_set_y: null argument"); return -1; }
+  HIPCHK(hipSetDevice(s->device));
+  if (int rc = h2d(s, u->y2, Y2, u->p.N2)) return rc;
+  u->p.Y2 = u->y2;
+  return 0;
+}
+
+int brr_session_predict_score(brr_session *s, const double *beta, double *out) {
+  Predict *u = predict_of(s, "predict_score", false);
+  if (!u) return -1;
+  if (!out) { set_error("predict_score: null argument"); return -1; }
+  if (!beta && !s->initialized) { set_error("predict_score: session not initialised (brr_session_init)"); return -1; }
+  HIPCHK(hipSetDevice(s->device));
+  const double *db = s->d.beta;
+  if (beta) {
+    if (int rc = h2d(s, u->beta_tmp, beta, s->M)) return rc;
+    db = u->beta_tmp;
+  }
+  HIPCHK(launch_predict_score(u->p, s->d, db, s->st));
+  if (int rc = d2h(s, out, u->p.g, u->p.N2)) return rc;
+  if (s->sum) s->sum->drain();  // (the stream has been synchronised)
+  u->drain();
+  return 0;
+}
+
+int brr_session_predict_begin(brr_session *s) {
+  Predict *u = predict_of(s, "predict_begin", false);
+  if (!u) return -1;
+  if (!s->initialized) { set_error("predict_begin: session not initialised (brr_session_init)"); return -1; }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->st));
+  u->release_acc();  // a second begin resets
+  PredDev &p = u->p;
+  const int64_t N2 = p.N2, nrg = (N2 + 255) / 256;
+  int rc = 0;
+  auto take = [&](auto **q, int64_t n) {
+    if (rc) { *q = nullptr; return; }
+    rc = dalloc(q, n);
+    if (!rc) {
+      u->acc_allocs.push_back((void *)*q);
+      if (hipMemsetAsync((void *)*q, 0, sizeof(**q) * (size_t)std::max<int64_t>(n, 1), s->st) != hipSuccess) rc = -2;
+    }
+  };
+  take(&p.gmean, N2);
+  take(&p.gM2, N2);
+  take(&p.rslab, PRED_SLAB * nrg);
+  take(&p.row, PRED_WIDTH);
+  take(&p.cnt, 4);
+  if (!rc && hipHostMalloc((void **)&u->pin, sizeof(double) * Predict::RING * PRED_WIDTH, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    u->pin = nullptr;
+    rc = -2;
+  }
+  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = -2;
+  if (rc) {
+    const std::string why = brr_last_error();
+    (void)hipStreamSynchronize(s->st);
+    (void)hipGetLastError();
+    u->release_acc();
+    set_error("predict_begin: the accumulators do not fit (%lld bytes: N2 %lld): %s",
+              (long long)(16 * N2 + 8 * (PRED_SLAB * nrg + PRED_WIDTH) + 16), (long long)N2, why.c_str());
+    return -2;
+  }
+  u->active = true;
+  return 0;
+}
+
+int brr_session_predict_accumulate(brr_session *s) {
+  if (!predict_of(s, "predict_accumulate", true)) return -1;
+  return predict_fold(s, s->iteration - 1);
+}
+
+int brr_session_predict_run(brr_session *s, int32_t max_iterations, int32_t burn_in, int32_t thinning) {
+  if (!predict_of(s, "predict_run", true)) return -1;
+  return brr::run_folding(s, "predict_run", max_iterations, burn_in, thinning);
+}
+
+int32_t brr_session_predict_count(brr_session *s) {
+  Predict *u = predict_of(s, "predict_count", true);
+  if (!u) return -1;
+  if (u->pending && predict_sync(s)) return -2;
+  return u->n;
+}
+
+int64_t brr_session_predict_get(brr_session *s, int32_t which, double *out) {
+  Predict *u = predict_of(s, "predict_get", true);
+  if (!u) return -1;
+  int64_t n = -1;
+  switch (which) {
+    case BRR_PRED_G_MEAN: case BRR_PRED_G_SD: case BRR_PRED_G_M2: n = u->p.N2; break;
+    case BRR_PRED_TRACE: n = (int64_t)u->n * PRED_WIDTH; break;
+    default: set_error("predict_get: unknown item %d", (int)which); return -1;
+  }
+  if (!out) return n;
+  if (int rc = predict_sync(s)) return rc;
+  int rc = 0;
+  switch (which) {
+    case BRR_PRED_G_MEAN: rc = d2h(s, out, u->p.gmean, n); break;
+    case BRR_PRED_G_M2: case BRR_PRED_G_SD:
+      rc = d2h(s, out, u->p.gM2, n);
+      if (!rc && which == BRR_PRED_G_SD)
+        for (int64_t i = 0; i < n; ++i) out[i] = u->n < 2 ? 0.0 : std::sqrt(out[i] / ((double)u->n - 1.0));
+      break;
+    case BRR_PRED_TRACE: std::copy(u->trace.begin(), u->trace.end(), out); break;
+  }
+  return rc ? rc : n;
+}
+
+int brr_session_predict_write(brr_session *s, const char *prefix) {
+  Predict *u = predict_of(s, "predict_write", true);
+  if (!u) return -1;
+  if (!prefix) { set_error("predict_write: null prefix"); return -1; }
+  auto get = [&](int which, std::vector<double> *v) -> int {
+    const int64_t n = brr_session_predict_get(s, which, nullptr);
+    if (n < 0) return (int)n;
+    v->assign((size_t)n, 0.0);
+    const int64_t r = n ? brr_session_predict_get(s, which, v->data()) : 0;
+    if (r < 0) set_error("predict_write: %s: %s", kPredictNames[which], std::string(brr_last_error()).c_str());
+    return r < 0 ? (int)r : 0;
+  };
+  auto open = [&](const char *ext) -> FILE * {
+    const std::string path = std::string(prefix) + ext;
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) set_error("predict_write: cannot open %s", path.c_str());
+    return f;
+  };
+  auto close = [&](FILE *f, const char *ext) -> int {
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) { set_error("predict_write: writing %s%s failed", prefix, ext); return -3; }
+    return 0;
+  };
+  std::vector<double> a, b;
+  {
+    if (int rc = get(BRR_PRED_G_MEAN, &a)) return rc;
+    if (int rc = get(BRR_PRED_G_SD, &b)) return rc;
+    FILE *f = open(".target.csv");
+    if (!f) return -3;
+    fputs("row,g_mean,g_sd\n", f);
+    for (int64_t i = 0; i < u->p.N2; ++i) fprintf(f, "%lld,%.17g,%.17g\n", (long long)i, a[(size_t)i], b[(size_t)i]);
+    if (int rc = close(f, ".target.csv")) return rc;
+  }
+  {
+    if (int rc = get(BRR_PRED_TRACE, &a)) return rc;
+    FILE *f = open(".target_trace.csv");
+    if (!f) return -3;
+    fputs("iteration,mean_g,var_g,mean_y,var_y,cov_yg,cor_yg,mse\n", f);
+    for (int r = 0; r < u->n; ++r)
+      for (int j = 0; j < PRED_WIDTH; ++j)
+        fprintf(f, "%.17g%c", a[(size_t)r * PRED_WIDTH + j], j + 1 == PRED_WIDTH ? '\n' : ',');
+    if (int rc = close(f, ".target_trace.csv")) return rc;
+  }
+  return 0;
+}
+
+int brr_session_predict_end(brr_session *s) {
+  if (!predict_of(s, "predict_end", true)) return -1;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->st));
+  s->pred->release_acc();
+  return 0;
+}
+
+int brr_session_predict_timing(brr_session *s, double *fold_ms_total, int64_t *folds) {
+  Predict *u = predict_of(s, "predict_timing", true);
+  if (!u) return -1;
+  if (int rc = predict_sync(s)) return rc;
+  for (auto &e : u->ev) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+    u->t_fold += ms;
+    u->n_fold++;
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
+  u->ev.clear();
+  if (fold_ms_total) *fold_ms_total = u->t_fold;
+  if (folds) *folds = u->n_fold;
+  return 0;
+}
+
+int32_t brr_predict_chunk(void) { return PRED_CHUNK; }
+int32_t brr_predict_row_tile(void) { return PRED_ROWS; }
 
 }  // extern "C"
 

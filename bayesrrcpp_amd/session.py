@@ -298,6 +298,111 @@ class Session:
     def summary_end(self):
         L.check(L.lib().brr_session_summary_end(self.h), "summary_end")
 
+    # -- out-of-sample prediction (brr_session_predict_*) --------------------------------------
+    def predict_upload_bed(self, bed, N2, bytes_per_col=None, table=None):
+        """Attach a target cohort of N2 rows as 2-bit codes: a PLINK .bed body (after the 3 magic bytes)
+        of this session's M markers, uint8 array of M * bytes_per_col bytes or (M, bytes_per_col).
+        table: (M, 4) float32 values of codes 00, 01 (missing), 10, 11; None = the training cohort's
+        table from upload_bed (training mean and sd, missing -> 0)."""
+        b = np.ascontiguousarray(bed, dtype=np.uint8)
+        if bytes_per_col is None:
+            bytes_per_col = b.shape[1] if b.ndim == 2 else (N2 + 3) // 4
+        if b.size < self.M * bytes_per_col:
+            raise ValueError("bed holds fewer than M * bytes_per_col bytes")
+        t = None
+        if table is not None:
+            t = np.ascontiguousarray(table, dtype=np.float32)
+            if t.shape != (self.M, 4):
+                raise ValueError(f"table must be {self.M} x 4")
+        L.check(L.lib().brr_session_predict_upload_bed(
+            self.h, b.ctypes.data_as(C.POINTER(C.c_uint8)), N2, bytes_per_col,
+            None if t is None else t.ctypes.data_as(C.POINTER(C.c_float))), "predict_upload_bed")
+        return self
+
+    def predict_upload_x(self, X2):
+        """Attach a target cohort the caller has scaled like the training X: N2 x M, stored dense f32."""
+        X2 = np.asarray(X2)
+        if X2.ndim != 2 or X2.shape[1] != self.M:
+            raise ValueError(f"X2 must be N2 x {self.M}")
+        n2 = X2.shape[0]
+        if X2.dtype == np.float32:
+            Xf = np.asfortranarray(X2)
+            L.check(L.lib().brr_session_predict_upload_x_f32(self.h, Xf.ctypes.data_as(C.POINTER(C.c_float)),
+                                                             n2, n2), "predict_upload_x_f32")
+        else:
+            Xd = np.asfortranarray(X2, dtype=np.float64)
+            L.check(L.lib().brr_session_predict_upload_x_f64(self.h, _d(Xd), n2, n2), "predict_upload_x_f64")
+        return self
+
+    @property
+    def predict_rows(self):
+        n = L.lib().brr_session_predict_rows(self.h)
+        if n < 0:
+            raise L.BrrError(f"predict_rows: {L.last_error()}")
+        return n
+
+    def predict_set_y(self, Y2):
+        """Validation phenotypes of the attached target (the trace's y columns)."""
+        Y2 = np.ascontiguousarray(Y2, dtype=np.float64)
+        if Y2.shape != (self.predict_rows,):
+            raise ValueError("Y2 must hold N2 values")
+        L.check(L.lib().brr_session_predict_set_y(self.h, _d(Y2)), "predict_set_y")
+        return self
+
+    def predict_score(self, beta=None):
+        """X2 beta (N2 doubles) for a beta of M values, or for the chain's current beta (None)."""
+        out = np.zeros(self.predict_rows)
+        b = None
+        if beta is not None:
+            b = np.ascontiguousarray(beta, dtype=np.float64)
+            if b.shape != (self.M,):
+                raise ValueError(f"beta must hold {self.M} values")
+        L.check(L.lib().brr_session_predict_score(self.h, None if b is None else _d(b), _d(out)), "predict_score")
+        return out
+
+    def predict_begin(self):
+        """Allocate (or reset) the accumulators over kept sweeps of the attached target."""
+        L.check(L.lib().brr_session_predict_begin(self.h), "predict_begin")
+        return self
+
+    def predict_accumulate(self):
+        """Score the current state and fold it in (no host synchronisation)."""
+        L.check(L.lib().brr_session_predict_accumulate(self.h), "predict_accumulate")
+        return self
+
+    def predict_run(self, max_iterations, burn_in, thinning):
+        """summary_run's loop: every active accumulator (prediction, and the summary's after
+        summary_begin) folds the state in at the kept sweeps."""
+        L.check(L.lib().brr_session_predict_run(self.h, max_iterations, burn_in, thinning), "predict_run")
+        return self
+
+    @property
+    def predict_count(self):
+        n = L.lib().brr_session_predict_count(self.h)
+        if n < 0:
+            raise L.BrrError(f"predict_count: {L.last_error()}")
+        return n
+
+    def predict(self, which):
+        """One item (L.PRED_*) as a numpy array; TRACE is kept x 8 (L.PRED_TRACE_HEADER)."""
+        n = L.lib().brr_session_predict_get(self.h, which, None)
+        if n < 0:
+            raise L.BrrError(f"predict({which}): {L.last_error()}")
+        out = np.zeros(n, dtype=np.float64)
+        if n and L.lib().brr_session_predict_get(self.h, which, _d(out)) < 0:
+            raise L.BrrError(f"predict({which}): {L.last_error()}")
+        return out.reshape(-1, len(L.PRED_TRACE_HEADER)) if which == L.PRED_TRACE else out
+
+    def predict_write(self, prefix):
+        """<prefix>.target.csv (row, g_mean, g_sd) and <prefix>.target_trace.csv."""
+        L.check(L.lib().brr_session_predict_write(self.h, str(prefix).encode()), "predict_write")
+
+    def predict_end(self):
+        L.check(L.lib().brr_session_predict_end(self.h), "predict_end")
+
+    def predict_detach(self):
+        L.check(L.lib().brr_session_predict_detach(self.h), "predict_detach")
+
     # -- instrumentation ----------------------------------------------------------------
     def set_timing(self, on: bool):
         L.check(L.lib().brr_session_set_timing(self.h, 1 if on else 0), "set_timing")
@@ -309,6 +414,12 @@ class Session:
                 "timing")
         return {"stream_ms": a.value, "stream_launches": na.value,
                 "solve_ms": b.value, "solve_launches": nb.value}
+
+    def predict_timing(self):
+        """HIP-event time of the prediction folds run while set_timing(True), since predict_begin."""
+        a, n = C.c_double(), C.c_int64()
+        L.check(L.lib().brr_session_predict_timing(self.h, C.byref(a), C.byref(n)), "predict_timing")
+        return {"fold_ms": a.value, "folds": n.value}
 
     @property
     def block_size(self):

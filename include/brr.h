@@ -317,11 +317,90 @@ int64_t brr_session_summary_get(brr_session *s, int32_t which, double *out /* NU
 int     brr_session_summary_write(brr_session *s, const char *prefix);
 int     brr_session_summary_end(brr_session *s);
 
+/* out-of-sample prediction (no reference counterpart): a target cohort of N2 individuals who were not
+ * in the training set, genotyped at this session's M markers, is attached to the session and scored
+ * on the device, g2 = X2 beta (N2 doubles) -- once for a given beta, or folded over the kept sweeps
+ * like the summaries above, which gives each individual's polygenic score with its posterior SD and,
+ * with validation phenotypes, the prediction accuracy per kept sweep.  Folding reads beta and mu on
+ * the device (two kernels on the session stream, no host synchronisation) and never changes the
+ * chain.
+ *   order   the marker axis is cut into chunks of brr_predict_chunk() (2048) consecutive markers.  A
+ *           row's chunk sum starts at 0 and takes acc = acc + (double)x * beta_j for the chunk's
+ *           markers in ascending order, product and sum rounded separately, markers with beta_j == 0
+ *           skipped; g2 is the chunk sums added to 0 in ascending chunk order.  The order depends on M
+ *           alone: two runs, the two target storages of the same values, and any N2 give a row the
+ *           same bits (bayesrrcpp_amd/predict.py restates it in numpy).
+ *   items   G_MEAN, G_SD, G_M2 per target row: the Welford mean, SD = sqrt(M2 / (n - 1)) (0 for n < 2
+ *           kept sweeps) and centred sum of squares of g2, as the summaries' g items.
+ *           TRACE kept x 8 row-major: [iteration, mean_g, var_g, mean_y, var_y, cov_yg, cor_yg, mse],
+ *           var_g = sum (g - mean_g)^2 / (N2 - 1), cov_yg = sum (y - mean_y)(g - mean_g) / (N2 - 1),
+ *           cor_yg = cov_yg / sqrt(var_y var_g) (0 when either variance is 0), mse = sum (y_i - mu -
+ *           g_i)^2 / N2 with the chain's mu of that sweep; N2 = 1 gives variances and covariance 0.
+ *           Without validation phenotypes every column that needs y (mean_y, var_y, cov_yg, cor_yg,
+ *           mse) is NaN.
+ *   memory  2-bit: M (roundup(ceil(N2 / 4), 64) + 16) bytes; f32: 4 M roundup(N2, 64) bytes; either:
+ *           8 (ceil(M / 2048) + 1) roundup(N2, 16) + 8 N2 + 8 M bytes of work space; accumulators 16 N2.
+ * Single-device sessions only: a column- or row-sharded session (shard_count > 1, row_shard_count >
+ * 1, brr_group members) is refused at attach, as summary_begin refuses it.  Every call below but the
+ * uploads fails (no device work) before a target is attached, and accumulate / run / count / get /
+ * write / end fail before predict_begin.
+ * Out of scope: fixed-effect covariates of the target (callers add mu and F2 alpha from the summary
+ * trace), the one-shot entry points and the R shim, and synthetic target cohorts. */
+enum brr_predict { BRR_PRED_G_MEAN = 0, BRR_PRED_G_SD, BRR_PRED_G_M2, BRR_PRED_TRACE /* kept x 8 row-major */ };
+/* markers per chunk of the summation order (2048), and the rows one workgroup of the score kernel
+ * covers on 2-bit codes (4096; f32 storage: a quarter): constants of the library */
+int32_t brr_predict_chunk(void);
+int32_t brr_predict_row_tile(void);
+/* attach a target of N2 rows as 2-bit codes + a 4-entry f32 value table per column, whatever the
+ * training storage.  bed: a PLINK .bed body packed as for brr_session_upload_bed, bytes_per_col >=
+ * ceil(N2 / 4) bytes per marker.  table: M x 4 floats, the value of codes 00, 01 (missing), 10, 11 of
+ * each marker; NULL = the training cohort's own table from brr_session_upload_bed (the training mean
+ * and sd, missing -> 0) -- an error when the training genotypes did not come from a .bed.  Rows >= N2
+ * of the last byte and the column padding are stored as code 01 whatever bits the caller left there,
+ * and take part in no result.  The byte size is checked in 64-bit-safe arithmetic against the free
+ * device memory before anything is allocated: a cohort that does not fit is refused with the sizes
+ * in brr_last_error() and the session stays usable.  An attach replaces an attached target (and its
+ * accumulators and phenotypes); a refused or failed attach leaves none. */
+int     brr_session_predict_upload_bed(brr_session *s, const uint8_t *bed, int64_t N2, int64_t bytes_per_col,
+                                       const float *table /* M x 4, or NULL */);
+/* attach a target the caller has already scaled like the training X: host column-major N2 x M with
+ * leading dimension ldx >= N2, stored dense f32 (f64 is converted as brr_session_upload_x_f64
+ * converts).  Size check and replacement as above. */
+int     brr_session_predict_upload_x_f64(brr_session *s, const double *X2, int64_t N2, int64_t ldx);
+int     brr_session_predict_upload_x_f32(brr_session *s, const float *X2, int64_t N2, int64_t ldx);
+/* free the target, its phenotypes and accumulators */
+int     brr_session_predict_detach(brr_session *s);
+int64_t brr_session_predict_rows(brr_session *s);                 /* N2 of the attached target, < 0 without one */
+/* optional validation phenotypes of the attached target (N2 doubles): the trace's y columns */
+int     brr_session_predict_set_y(brr_session *s, const double *Y2);
+/* out = X2 beta (N2 doubles) for a host beta of M doubles, or for the chain's current beta on the
+ * device when beta is NULL (an initialised session).  Needs no accumulators and changes nothing. */
+int     brr_session_predict_score(brr_session *s, const double *beta /* M, or NULL */, double *out /* N2 */);
+/* allocate and zero the accumulators of an initialised session (a second begin resets them) */
+int     brr_session_predict_begin(brr_session *s);
+/* fold the current state in; its trace row's iteration is brr_session_iteration() - 1 */
+int     brr_session_predict_accumulate(brr_session *s);
+/* brr_session_summary_run's loop (shared): at each kept sweep every active accumulator -- these, and
+ * the summary's when brr_session_summary_begin was called -- folds the state in, so one chain yields
+ * both; brr_session_summary_run does the same with a target attached and begun */
+int     brr_session_predict_run(brr_session *s, int32_t max_iterations, int32_t burn_in, int32_t thinning);
+int32_t brr_session_predict_count(brr_session *s);                /* kept sweeps so far */
+/* returns the item's length in doubles (out == NULL: only that), < 0 on error; synchronises */
+int64_t brr_session_predict_get(brr_session *s, int32_t which, double *out /* NULL = size */);
+/* <prefix>.target.csv (row, g_mean, g_sd) and <prefix>.target_trace.csv (the trace's eight named
+ * columns): one header line, %.17g values, 0-based rows */
+int     brr_session_predict_write(brr_session *s, const char *prefix);
+/* free the accumulators; the target stays attached */
+int     brr_session_predict_end(brr_session *s);
+
 /* instrumentation: per-launch HIP-event timing of the streaming kernel (dots + residual
  * update), accumulated over the sweeps run while enabled. */
 int brr_session_set_timing(brr_session *s, int32_t on);
 int brr_session_timing(brr_session *s, double *stream_ms_total, int64_t *stream_launches,
                        double *solve_ms_total, int64_t *solve_launches);
+/* the same for the prediction folds (score + row kernel of brr_session_predict_accumulate / _run)
+ * run while timing is enabled, totals since brr_session_predict_begin; synchronises */
+int brr_session_predict_timing(brr_session *s, double *fold_ms_total, int64_t *folds);
 /* algorithmic bytes of one streaming launch = 4 * N * block_size */
 int64_t brr_session_block_size(brr_session *s);
 int brr_session_synchronize(brr_session *s);
